@@ -15,6 +15,12 @@ Multi-GPU, two launch forms, both weak scaling by default (1M series per GPU):
     rank its own shard, partial states all-gathered over RCCL (tsdbhip_partials_* in the C ABI).
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+
+A plain run (`--gpus N --steps K --warmup W`) generates the store, warms up, times the K steps
+and prints the line.  `--full` adds what takes runs of its own: the parity checks against the
+one-GPU reference, BASELINE config 3 (and config 5 on N > 1 GPUs) in `extra`, the CPU baseline
+and the rocprofv3 PMC passes behind roofline.traffic.  `--dump-outputs DIR` writes the last timed
+step's result as DIR/*.npy (dump_outputs), the same for the same arguments.
 """
 from __future__ import annotations
 
@@ -47,14 +53,22 @@ def parse():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --series per GPU (each rank its own store); strong: --series in total, one global "
                          "store split over the ranks (tsdbhip_synth_shard), e.g. config 3's 10M series 1/2/4/8 ways")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline work (s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 FETCH/WRITE_SIZE child passes")
-    ap.add_argument("--no-config3", action="store_true", help="skip the config-3 (10M series) block in `extra`")
-    ap.add_argument("--no-config5", action="store_true", help="--gpus N > 1: skip the config-5 block in `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the parity checks against the one-GPU reference, the config-3 / "
+                         "config-5 blocks in `extra`, the CPU baseline and the rocprofv3 PMC passes (each can be "
+                         "dropped again with its --no-* switch).  Without --full a run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's result (what the caller of the query "
+                         "receives) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline work (s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 FETCH/WRITE_SIZE child passes")
+    ap.add_argument("--no-config3", action="store_true", help="--full: skip the config-3 (10M series) block in `extra`")
+    ap.add_argument("--no-config5", action="store_true", help="--full, --gpus N > 1: skip the config-5 block in `extra`")
     ap.add_argument("--c5-series", type=int, default=10_000_000, help=argparse.SUPPRESS)   # rehearsals only
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the parity checks against the one-GPU reference (exploratory runs only)")
+                    help="--full: skip the parity checks against the one-GPU reference (exploratory runs only)")
     ap.add_argument("--transport", choices=["auto", "rccl", "copy"], default="auto",
                     help="multi-device context (--gpus N, no launcher): RCCL send / recv or peer copies")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -63,7 +77,48 @@ def parse():
     ap.add_argument("--c3-series", type=int, default=10_000_000, help=argparse.SUPPRESS)   # rehearsals only
     ap.add_argument("--md-timeout", type=float, default=480.0,
                     help="--gpus N > 1: seconds the multi-device run may take before it is retried over peer copies")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline alone
+        args.no_parity = args.no_config3 = args.no_config5 = args.no_cpu_baseline = args.no_pmc = True
+    return args
+
+
+# a dump may take 64 MB: 4 float64 arrays per point (48 MB) + 3 per group (12 MB)
+DUMP_MAX_POINTS = 1_500_000
+DUMP_MAX_GROUPS = 500_000
+
+
+def result_copy(groups):
+    """[(group id, ts, bits, is_int)] copies of a result, in the order the caller received it
+    (the library's arrays are views that die with the result)."""
+    import numpy as np
+    return [(int(g), np.array(ts), np.array(bits), np.array(isi)) for g, ts, bits, isi in groups]
+
+
+def dump_outputs(path: str, groups):
+    """--dump-outputs: the last timed step's result as float64 .npy files under `path`:
+    group_id / group_len per group in the order received, and per point, the groups end to
+    end: timestamp_ms, value (an integer result as its value, a floating one from its bits),
+    is_int.  A result of more than DUMP_MAX_POINTS points is written as a fixed seeded sample of
+    its points, their positions in point_index; one of more than DUMP_MAX_GROUPS groups with a
+    fixed seeded sample of the per-group arrays, their positions in group_index."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    gid = np.array([g for g, _, _, _ in groups], dtype=np.float64)
+    glen = np.array([len(ts) for _, ts, _, _ in groups], dtype=np.float64)
+    gidx = np.arange(len(gid), dtype=np.int64)
+    if len(gidx) > DUMP_MAX_GROUPS:
+        gidx = np.sort(np.random.default_rng(0x5EED).choice(len(gidx), DUMP_MAX_GROUPS, replace=False))
+    ts = np.concatenate([np.asarray(t, dtype=np.int64) for _, t, _, _ in groups] or [np.zeros(0, np.int64)])
+    bits = np.concatenate([np.asarray(b).view(np.int64) for _, _, b, _ in groups] or [np.zeros(0, np.int64)])
+    isi = np.concatenate([np.asarray(i) for _, _, _, i in groups] or [np.zeros(0, np.uint8)]).astype(bool)
+    value = np.where(isi, bits.astype(np.float64), bits.view(np.float64))
+    idx = np.arange(len(ts), dtype=np.int64)
+    if len(idx) > DUMP_MAX_POINTS:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(len(idx), DUMP_MAX_POINTS, replace=False))
+    for name, a in (("group_index", gidx), ("group_id", gid[gidx]), ("group_len", glen[gidx]), ("point_index", idx),
+                    ("timestamp_ms", ts[idx]), ("value", value[idx]), ("is_int", isi[idx])):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def host_cpu():
@@ -962,13 +1017,20 @@ def main_md(args):
         eng.run(q)
     eng.sync()
     stats = []
+    res = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.run(q)
+    for i in range(args.steps):
+        if i + 1 < args.steps:
+            eng.run(q)   # (the result freed before the next step, as a caller that consumed it would)
+        else:
+            res = eng.run(q)   # the last step's result stays for --dump-outputs
         ranks = md_step_stats(eng, stats)
     eng.sync()
     elapsed = time.perf_counter() - t0
     tm = eng.timing()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_copy(res))
+    del res
     ms_per_step = elapsed * 1000.0 / args.steps
     value = tm.datapoints / (ms_per_step / 1000.0)
     # per device: its k_fast hipEvent time, its algorithmic bytes
@@ -1003,7 +1065,8 @@ def main_md(args):
         "transport_note": note,
         "rccl_failed": False,
         "rccl_ranks": ranks,
-        "parity_ok": ok,
+        "full": args.full,
+        "parity_ok": ok if args.full else None,
         "parity": parity,
         "exchange_ms": tm.exchange_ms,
         "stages": md_stages(stats),
@@ -1311,9 +1374,13 @@ def main():
     kernel_ms = []
     fast_ms = []
     reduce_ms = []
+    res = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if i + 1 < args.steps:
+            step()   # (the result freed before the next step, as a caller that consumed it would)
+        else:
+            res = step()   # the last step's result stays for --dump-outputs
         tm = eng.timing()
         kernel_ms.append(tm.decode_downsample_ms)
         fast_ms.append(tm.fast_ms)
@@ -1321,6 +1388,9 @@ def main():
     L.sync(eng)
     elapsed = L.max(time.perf_counter() - t0)
     tm = eng.timing()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result_copy(res))
+    del res
     ms_per_step = elapsed * 1000.0 / args.steps
     dps_step = L.sum(int(tm.datapoints))   # datapoints of every rank's shard
     value = dps_step / (ms_per_step / 1000.0)
@@ -1344,7 +1414,7 @@ def main():
     ok = parity_all_ok(parity, extra)
     if rank == 0:
         cpu = None if args.no_cpu_baseline or world > 1 else cpu_baseline(args, args.cpu_seconds)
-        traffic, traffic_note = (None, "not collected (--no-pmc or N>1)")
+        traffic, traffic_note = (None, "not collected (--no-pmc or N>1)" if args.full else "not collected (needs --full)")
         if not args.no_pmc and world == 1:
             traffic, traffic_note = pmc_traffic(args, f"void tsdb::{kname}")
             if extra is not None and "config3" in extra:   # config 3: both k_short row classes of a step
@@ -1370,7 +1440,8 @@ def main():
                          "brings freshly scanned cells",
             "launch": ("one process per GPU (torch.distributed.run), partial states all-gathered over "
                        f"{'RCCL' if L.backend == 'nccl' else L.backend}") if L.dist is not None else "one process, one GPU",
-            "parity_ok": ok,
+            "full": args.full,
+            "parity_ok": ok if args.full else None,
             "parity": parity,
             "config": {
                 "workload": workload_label(args),

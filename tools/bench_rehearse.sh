@@ -13,11 +13,11 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 TR="python -u -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
-C="--steps 5 --warmup 2 --no-pmc --no-cpu-baseline --c3-series 2000000 --c5-series 1000000"
+C="--full --steps 5 --warmup 2 --no-pmc --no-cpu-baseline --c3-series 2000000 --c5-series 1000000"
 for s in $steps; do
   echo "== $s"
   case $s in
-    n1)    timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-pmc --no-cpu-baseline > $out/$s.jsonl 2> $out/$s.err ;;
+    n1)    timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-pmc --no-cpu-baseline > $out/$s.jsonl 2> $out/$s.err ;;
     rccl1) TSDBHIP_BENCH_FORCE_DIST=1 timeout -k 10 400 $TR --nproc-per-node 1 --master-port 29511 bench.py $C > $out/$s.jsonl 2> $out/$s.err ;;
     gloo2) TSDBHIP_BENCH_DIST=gloo TSDBHIP_BENCH_DEVICES=0,0 timeout -k 10 500 $TR --nproc-per-node 2 --master-port 29512 \
              bench.py --gpus 2 --series 500000 $C > $out/$s.jsonl 2> $out/$s.err ;;

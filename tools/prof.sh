@@ -6,7 +6,7 @@ tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 run() {  # name, rocprof args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" --output-format csv -d $out/$name -o run -- $B > $out/$name.log 2>&1

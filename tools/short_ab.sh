@@ -4,7 +4,7 @@ set -o pipefail
 out=gpurun_out/$1; B=$2; mkdir -p $out; export TMPDIR=/tmp
 for run in a1 b1 a2 b2; do
   case $run in a*) L=opentsdb_amd/lib/libtsdbhip.so;; b*) L=$B;; esac
-  TSDBHIP_LIB=$L timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-pmc --no-cpu-baseline > $out/$run.json 2> $out/$run.err || { tail $out/$run.err; exit 1; }
+  TSDBHIP_LIB=$L timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-pmc --no-cpu-baseline > $out/$run.json 2> $out/$run.err || { tail $out/$run.err; exit 1; }
 done
 python3 -c "
 import json
