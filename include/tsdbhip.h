@@ -194,7 +194,9 @@ const char* tsdbhip_last_error(void);
 /* Developer options (no reference counterpart): kernel-choice switches that the parity tests
  * use to force an alternative kernel onto the same data (the general kernel, a sequential path,
  * small compaction chunks, ...), by name without a prefix: FAST, SHORT, ROWS, HWIN, SEQ,
- * SEQ_ROWS, SEQ_WAVE, INDEX_GENERIC, CMP_CHUNK, CMP_ROWS, CMP_ONEPASS, PCT_ROWS, PCT_KEYS,
+ * SEQ_ROWS, SEQ_WAVE, INDEX_GENERIC, INDEX_FUSED (0: the load-time index classifies first and
+ * allocates the int16 value copy late, as a store with no spare memory does), CMP_CHUNK,
+ * CMP_ROWS, CMP_ONEPASS, PCT_ROWS, PCT_KEYS,
  * PCT_VONLY, PCT_V6, SEL_FUSED, SEL_COLS, SEL_WIN, SEL_WAVE, SEL_REG, SELOPS, RAW_LERPW,
  * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT, TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
@@ -706,6 +708,15 @@ int tsdbhip_sync(tsdbhip_ctx* ctx);
  * batch, rows in resident order -- datapoints, RowDesc flags, exactness-certificate lsb and
  * max |value|.  Any pointer may be null. */
 int tsdbhip_debug_rows(tsdbhip_ctx* ctx, uint32_t* ndp, uint32_t* flags, int32_t* lsb, double* absmax);
+
+/* Test hook (no reference counterpart): the routes the last load's index took.  cnt[0..10] are
+ * the rows of each index class (0: the sequential kernel's, 1 + 5 (4-byte qualifiers) + value
+ * length slot: a class kernel's), cnt[12] / cnt[13] the rows k_index_short took (4-byte values /
+ * 1-2-byte integers), cnt[14] the rows it handed back to the sequential kernel; *fused: 1 when the
+ * classifying pass indexed the short rows itself (index_fused), 0 when the classes came first
+ * (option INDEX_FUSED = 0, or no room for the int16 value copy up front).  All zeros under option
+ * INDEX_GENERIC.  A pure read.  Either pointer may be null. */
+int tsdbhip_debug_index(tsdbhip_ctx* ctx, uint32_t cnt[16], int* fused);
 
 /* Test hook (no reference counterpart): how many percentile / median group-by queries took the
  * sampled-window select, and how many of those fell back to the full path (a window that missed

@@ -473,6 +473,8 @@ struct tsdbhip_ctx {
   int64_t redo_other = 0;                // + tiles of neither row class (k_grid only)
   tsdbhip_timing timing{};
   double index_ms = 0;                   // k_index (+ val2 pass) of the last load
+  uint32_t idx_cnt[16] = {};             // the last load's index routes (tsdbhip_debug_index): class counts, hand-backs
+  bool idx_fused = false;                // the last load's short rows were indexed by the classifying pass
   double compact_ms = 0;                 // k_compact pipeline of the last tsdbhip_load_cells
   int64_t fused_n = 0;                   // queries of the fused multi-aggregator pass being collected
   // account() cache (invalidated by every load)
@@ -608,7 +610,7 @@ namespace {
 // stored as value + 1 so that the zero-initialised table means "every option unset"
 std::atomic<int64_t> g_opts[OPT_COUNT];
 const char* const kOptNames[OPT_COUNT] = {
-    "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "CMP_CHUNK", "CMP_ROWS",
+    "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
     "HIST_WS", "HIST_LAYOUT", "TRACE", "DBG"};
@@ -1002,7 +1004,8 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   bool fused = false;
   if (!generic) {
     size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > c->qual_bytes + BLOB_SLACK + ((size_t)8 << 30)) {
+    if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess &&
+        fr > c->qual_bytes + BLOB_SLACK + ((size_t)8 << 30)) {
       HIP_OK(c->val2.ensure(c->qual_bytes + BLOB_SLACK));
       fused = true;
     }
@@ -1025,6 +1028,16 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   std::vector<RowDesc> back(c->n_rows);
   if (c->n_rows)
     HIP_OK(hipMemcpyAsync(back.data(), c->rows.p, c->n_rows * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  // tsdbhip_debug_index: the class counts; k_index_short's hand-backs are counted on the device
+  // only when it ran from the hints (index_fused has read its own), so that word rides along
+  std::memset(c->idx_cnt, 0, sizeof(c->idx_cnt));
+  c->idx_fused = fused;
+  if (!generic) {
+    std::memcpy(c->idx_cnt, ik.cnt, sizeof(c->idx_cnt));
+    if (!fused) c->idx_cnt[IDX_C_FAIL] = 0;
+    if (!fused && ik.short_rows)
+      HIP_OK(hipMemcpyAsync(&c->idx_cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
+  }
   HIP_OK(hipStreamSynchronize(c->stream));
   float t_index = 0, t_val2 = 0, t_cls = 0;
   (void)hipEventElapsedTime(&t_cls, c->ev[0], c->ev[2]);
@@ -2552,6 +2565,16 @@ extern "C" int tsdbhip_debug_sel_window(tsdbhip_ctx* c, int64_t* runs, int64_t* 
   CtxLock lk(c);
   if (runs) *runs = c->win_runs;
   if (misses) *misses = c->win_misses;
+  return 0;
+}
+
+// Test hook: the routes the last load's index took (class counts, k_index_short's hand-backs).
+extern "C" int tsdbhip_debug_index(tsdbhip_ctx* c, uint32_t cnt[16], int* fused) {
+  MD_REFUSE(c, "tsdbhip_debug_index");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  CtxLock lk(c);
+  if (cnt) std::memcpy(cnt, c->idx_cnt, sizeof(c->idx_cnt));
+  if (fused) *fused = c->idx_fused ? 1 : 0;
   return 0;
 }
 
@@ -4351,6 +4374,9 @@ int run_raw(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, tsdbhip_resul
     for (int64_t r = c->h_srp[s]; r < c->h_srp[s + 1]; r++) {
       if ((int64_t)c->h_base[r] < P.ss || (int64_t)c->h_base[r] >= P.se) continue;
       const uint32_t f = c->h_flags[r];
+      // a malformed cell in the scan: k_raw_decode would skip the row and leave its points
+      // unwritten, and k_raw_rank indexes the timestamp bitmap by them
+      if (f & ROW_ERR) return fail(TSDB_E_ILLEGAL_DATA, "malformed cell in the scanned rows");
       if (f & ROW_UNSORTED) uns = true;
       if ((f & ROW_QW_MASK) != 2) all_s = false;
       if (f & ROW_ALLF) any_float = true;

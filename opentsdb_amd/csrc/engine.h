@@ -560,6 +560,9 @@ struct IndexBufs {
   int32_t* list;     // [n_rows] rows by class
   uint32_t* cnt;     // [16] class counts / list cursors
 };
+// IndexClasses.cnt / IndexBufs.cnt slots past the classes: k_index_short's rows (4-byte values /
+// 1-2-byte integers) and the rows it handed back to k_index_generic
+static constexpr int IDX_C_SHORT4 = 12, IDX_C_SHORTV = 13, IDX_C_FAIL = 14;
 struct IndexClasses {
   uint32_t cnt[16];
   uint32_t off[16];

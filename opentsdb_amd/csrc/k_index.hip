@@ -35,9 +35,6 @@ namespace tsdb {
 static constexpr int IDX_STAGE = 4224;   // bytes of value staging per wave: 512 x 8 B + alignment
 static constexpr int IDX_NCLS = 11;      // 0 generic, 1 + qwi * 5 + li (qwi: 2 / 4 bytes; li: var, 1, 2, 4, 8)
 static constexpr uint8_t HINT_SHORT = 0x80;   // hint bit: the row is k_index_short's (low bits: its class)
-// IndexBufs.cnt slots past the classes: k_index_short's rows (4-byte values / 1-2-byte integers)
-// and the rows it handed back to k_index_generic
-static constexpr int IDX_C_SHORT4 = 12, IDX_C_SHORTV = 13, IDX_C_FAIL = 14;
 #ifndef IDX_SHORT_D
 #define IDX_SHORT_D 2   // k_index_short's load ring depth
 #endif
@@ -102,7 +99,7 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
     ok4 = __all(ok4);
     lmin2 = wave_min(lmin2); lmax2 = wave_max(lmax2);
     lmin4 = wave_min(lmin4); lmax4 = wave_max(lmax4);
-    uint32_t flags = 0, ndp = 0;
+    uint32_t flags = 0, ndp = 0, cut = 0;
     if (ok2) {
       ndp = qlen / 2; flags = 2;
       if (lmin2 == lmax2) flags |= (uint32_t)lmin2 << ROW_VL_SHIFT;
@@ -119,11 +116,15 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
           ndp++;
           i += w;
         }
+        // bytes left over (an odd length, a 4-byte qualifier cut short): RowSeq.Iterator.next reads
+        // past the array after the last whole datapoint -- a malformed cell
+        cut = i < qlen;
       }
       ndp = __shfl(ndp, 0, 64);
+      cut = __shfl(cut, 0, 64);
     }
     // walk every datapoint: validate qualifier/value lengths, certificate stats
-    bool bad = qlen == 0;
+    bool bad = qlen == 0 || cut != 0;
     bool allf = true, alli = true, vmax2 = true, hasnan = false, negz = false, unsorted = false;
     int lsbmin = INT32_MAX;
     double amax = 0.0;

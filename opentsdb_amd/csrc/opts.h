@@ -18,6 +18,7 @@ enum Opt : int {
   OPT_SEQ_ROWS,       // 0: no k_seq_rows (k_seq_dense instead)
   OPT_SEQ_WAVE,       // 0: k_seq_dense (a series a lane) instead of k_seq_wave
   OPT_INDEX_GENERIC,  // 1: the sequential per-datapoint index path for every row
+  OPT_INDEX_FUSED,    // 0: classes first, then k_index_short from the hints (the path of stores with no room for val2 up front)
   OPT_CMP_CHUNK,      // > 0: compaction chunks of at most this many columns / datapoints
   OPT_CMP_ROWS,       // 0: the global-sort compaction pipeline instead of the per-row one
   OPT_CMP_ONEPASS,    // 0: the two-pass per-row compaction

@@ -29,7 +29,7 @@ EXPORTS = [
     "tsdbhip_run_partials", "tsdbhip_run_partials_multi", "tsdbhip_finalize", "tsdbhip_sync", "tsdbhip_rollup_interval_parse",
     "tsdbhip_rollup_basetime", "tsdbhip_rollup_qualifier", "tsdbhip_rollup_run", "tsdbhip_rollup_download",
     "tsdbhip_sel_layout", "tsdbhip_sel_run_values", "tsdbhip_sel_select", "tsdbhip_assemble", "tsdbhip_run_multi",
-    "tsdbhip_debug_rows", "tsdbhip_debug_sel_window", "tsdbhip_shard_bounds", "tsdbhip_load_shard", "tsdbhip_synth_shard",
+    "tsdbhip_debug_rows", "tsdbhip_debug_index", "tsdbhip_debug_sel_window", "tsdbhip_shard_bounds", "tsdbhip_load_shard", "tsdbhip_synth_shard",
     "tsdbhip_load_rollup", "tsdbhip_load_cells", "tsdbhip_load_histograms", "tsdbhip_hist_run",
     "tsdbhip_hist_run_range", "tsdbhip_hist_result_free", "tsdbhip_expr_map", "tsdbhip_expr_zip", "tsdbhip_expr_topn",
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
@@ -38,11 +38,12 @@ EXPORTS = [
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
-OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "CMP_CHUNK", "CMP_ROWS",
+OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
            "HIST_WS", "HIST_LAYOUT", "TRACE", "DBG"]
 
+IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
 MD_AUTO, MD_COPY, MD_RCCL = -1, 0, 1                               # tsdbhip.h TSDB_MD_*
 
@@ -145,6 +146,7 @@ def lib():
         L.tsdbhip_rollup_run.argtypes = [vp, C.POINTER(abi.RollupSpec), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
         L.tsdbhip_rollup_download.argtypes = [vp] + [C.c_void_p] * 5
         L.tsdbhip_debug_rows.argtypes = [vp] + [C.c_void_p] * 4
+        L.tsdbhip_debug_index.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int)]
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_shard_bounds.argtypes = [C.POINTER(abi.Batch), C.c_int, C.c_int, C.c_void_p]
         L.tsdbhip_load_shard.argtypes = [vp, C.POINTER(abi.Batch), C.c_int, C.c_int64, C.c_int64]
@@ -194,19 +196,22 @@ def reset_options() -> None:
 
 
 class options:
-    """Context manager: developer options set for the block, reset after it."""
+    """Context manager: developer options set for the block, their previous values restored
+    after it (so blocks nest)."""
 
     def __init__(self, **kw):
         self.kw = kw
+        self.old = {}
 
     def __enter__(self):
+        self.old = {k: get_option(k) for k in self.kw}
         for k, v in self.kw.items():
             set_option(k, v)
         return self
 
     def __exit__(self, *exc):
-        for k in self.kw:
-            set_option(k, -1)
+        for k, v in self.old.items():
+            set_option(k, v)
         return False
 
 
@@ -477,6 +482,14 @@ class Engine:
                                         amax.ctypes.data))
         k = nr.value
         return ndp[:k], flags[:k], lsb[:k], amax[:k]
+
+    def debug_index(self):
+        """Test hook: (cnt, fused) of the last load's index -- cnt[0..10] rows by index class,
+        cnt[IDX_C_SHORT4] / cnt[IDX_C_SHORTV] k_index_short's rows, cnt[IDX_C_FAIL] the rows it
+        handed back; fused: the classifying pass indexed the short rows itself."""
+        cnt, fused = np.zeros(16, np.uint32), C.c_int()
+        _check(lib().tsdbhip_debug_index(self.ctx, cnt.ctypes.data, C.byref(fused)))
+        return cnt, fused.value
 
     def debug_sel_window(self):
         """Test hook: (runs, misses) of the sampled-window percentile group-by select."""

@@ -807,10 +807,13 @@ static ref_view* make_span(int64_t n_rows, const uint32_t* base_time, const uint
     nr.qlen = (int64_t)(qual_off[r + 1] - qual_off[r]);
     nr.v = val + val_off[r];
     nr.vlen = (int64_t)(val_off[r + 1] - val_off[r]);
+    /* (:208 reads rowseq.timestamp(0) for every row, the span's first included: a cell with no
+     * qualifier fails there -- ArrayIndexOutOfBounds in size() -- before any datapoint is read) */
+    const int64_t first_ts = row_timestamp(&nr, 0);
     if (s->nrows > 0) {
       const rowseq* last = &s->rows[s->nrows - 1];
       const int64_t last_ts = row_timestamp(last, row_size(last) - 1);
-      if (last_ts >= row_timestamp(&nr, 0)) {
+      if (last_ts >= first_ts) {
         int64_t j = 0;
         for (; j < s->nrows; j++) if (s->rows[j].base == nr.base) break;
         if (j < s->nrows) { rowseq_merge(s, &s->rows[j], &nr); continue; }

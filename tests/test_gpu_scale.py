@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from opentsdb_amd import abi, synth
-from opentsdb_amd.engine import get_option, set_option
+from opentsdb_amd.engine import options
 from oracle import oracle as O
 from tests.test_gpu_fast import assert_bit_equal
 from tests.test_gpu_parity import assert_groups_match, T0
@@ -41,14 +41,7 @@ def eng():
 
 
 def _with_generic(flag: bool):
-    class Ctx:
-        def __enter__(self):
-            self.old = get_option("INDEX_GENERIC")
-            set_option("INDEX_GENERIC", 1 if flag else 0)
-
-        def __exit__(self, *a):
-            set_option("INDEX_GENERIC", self.old)
-    return Ctx()
+    return options(INDEX_GENERIC=1 if flag else 0)
 
 
 def fuzz_batch(seed: int, n_series: int = 400):

@@ -56,6 +56,24 @@ def test_set_get_reset():
         E.reset_options()
 
 
+def test_options_nest_and_restore_previous_values():
+    """engine.options puts back what it found, not -1: an inner block leaves the outer block's
+    (and a plain set_option's) values standing, also when the block raises."""
+    try:
+        E.set_option("SEL_WIN", 2)
+        with E.options(INDEX_GENERIC=1, FAST=0):
+            with E.options(INDEX_GENERIC=0, INDEX_FUSED=0, SEL_WIN=0):
+                assert [E.get_option(n) for n in ("INDEX_GENERIC", "INDEX_FUSED", "SEL_WIN", "FAST")] == [0, 0, 0, 0]
+            assert [E.get_option(n) for n in ("INDEX_GENERIC", "INDEX_FUSED", "SEL_WIN", "FAST")] == [1, -1, 2, 0]
+            with pytest.raises(RuntimeError):
+                with E.options(FAST=1):
+                    raise RuntimeError("x")
+            assert E.get_option("FAST") == 0
+        assert [E.get_option(n) for n in ("INDEX_GENERIC", "INDEX_FUSED", "SEL_WIN", "FAST")] == [-1, -1, 2, -1]
+    finally:
+        E.reset_options()
+
+
 @pytest.mark.parametrize("name", ["TSDBHIP_FAST", "fast", "", "SEL_T", "HIST_DBG", "PULL"])
 def test_unknown_or_removed_options_refused(name):
     with pytest.raises(E.EngineError) as ei:
