@@ -379,7 +379,7 @@ int tsdbhip_assemble(tsdbhip_ctx* ctx, const tsdbhip_query* q, int64_t n_groups_
  * device copies when a device repeats (several shards on one GPU); TSDB_MD_RCCL / TSDB_MD_COPY
  * force one.
  * Entry points bound to one device's resident store (load_shard, synth_shard, batch
- * downloads, the per-rank partials / sel exchange, debug_rows) return TSDB_E_NOT_IMPLEMENTED on
+ * downloads, the per-rank partials / sel exchange, tsdbhip_preagg_run / _download, debug_rows) return TSDB_E_NOT_IMPLEMENTED on
  * such a context.  tsdbhip_load_rollup shards a rollup batch and tsdbhip_load_cells a compaction
  * scan (each device compacts its series' rows) as tsdbhip_load shards a batch;
  * tsdbhip_rollup_run generates every device's series' rollup cells on that device and
@@ -452,6 +452,61 @@ int tsdbhip_rollup_run(tsdbhip_ctx* ctx, const tsdbhip_rollup_spec* spec, int64_
  * val_off[n_cells + 1], value[value_bytes]. */
 int tsdbhip_rollup_download(tsdbhip_ctx* ctx, int32_t* series, uint32_t* base_time, uint8_t* qualifier,
                             uint64_t* val_off, uint8_t* value);
+
+/* ---- pre-aggregate generation (the group-by tables) ----------
+ * The group-by half of the 2.4 rollup storage model: "SUM over hosts per colo, every hour" is
+ * stored as a series tagged _aggregate=SUM in the interval's group-by table
+ * (TSDB.addAggregatePointInternal with is_groupby, src/core/TSDB.java:1441-1588;
+ * RollupInterval.getGroupbyTable).  The reference ingests such points but never computes them,
+ * so the cells are defined by the query path it does define.  For function i, the query
+ *   start_time = start_s, end_time = end_s - 1, aggregator = groupby_aggregator,
+ *   ds_function = func[i], ds_fill = NONE, ds_interval_ms = interval.interval_s * 1000
+ *   (form B: ds_interval_ms), flags = flags, no rate
+ * over the resident batch: the cells of function i are exactly the DataPoints tsdbhip_run
+ * returns for it -- one cell per emitted (group, timestamp), interpolated (LERP) contributions
+ * included.  Groups that emit nothing have no cells; series without a group (id -1) take no
+ * part.  Cells are ordered by (function index, batch group id, time).
+ *   form A, interval.interval_s != 0: the interval's group-by table --
+ *     row base   getRollupBasetime(ts, interval)
+ *     qualifier  the 3-byte buildRollupQualifier(ts, base, flags, agg_id[i], interval);
+ *   form B, interval.interval_s == 0: the default interval's group-by table, ordinary
+ *     datapoint columns (TSDB.java:1531-1535,1560) --
+ *     row base   ts - ts % 3600
+ *     qualifier  the 2-byte Internal.buildQualifier(ts in seconds, flags);
+ *     ds_interval_ms % 1000 != 0 -> TSDB_E_ILLEGAL_ARGUMENT (addAggregatePointInternal refuses
+ *     millisecond timestamps, :1464).
+ * Value, both forms: downsampled group results are always doubles (Downsampler.isInteger), so
+ * NO integer cell is ever written -- a float32 when (float) v == v (flags 0xB), else a float64
+ * (flags 0xF), tsdbhip_rollup_run's rule for non-integer series.  A NaN or infinite emitted
+ * point -> TSDB_E_ILLEGAL_ARGUMENT and no output.
+ * TSDB_E_ILLEGAL_ARGUMENT: a null argument, an invalid interval, n_funcs out of range, a
+ * function outside the form's set, groupby_aggregator NONE or unknown, a bad time range, an
+ * unknown flag.  TSDB_E_NOT_IMPLEMENTED: a resident rollup batch (tsdbhip_load_rollup), a
+ * multi-device context, a plan that is not a fixed epoch-aligned grid.
+ * The functions' queries run on the device as tsdbhip_run runs them; their dense results never
+ * visit the host: one sizing pass, one scan and one write pass encode every function's cells,
+ * and the call synchronises with the device once for them.  The output stays on the device,
+ * in buffers of its own (a tsdbhip_rollup_run result is not disturbed), until
+ * tsdbhip_preagg_download, the next tsdbhip_preagg_run, or a load.  tsdbhip_last_timing after
+ * the call: decode_downsample_ms = the functions' query passes, group_reduce_ms = the encode
+ * stage (size + scan + write). */
+typedef struct {
+  tsdbhip_rollup_interval interval;  /* interval.interval_s == 0: no rollup interval (form B) */
+  int64_t ds_interval_ms;            /* form B only: the downsampling interval */
+  int64_t start_s, end_s;            /* as tsdbhip_rollup_spec */
+  int32_t groupby_aggregator;        /* TSDB_AGG_*: anything tsdbhip_run accepts with a downsampler, except NONE */
+  int32_t flags;                     /* TSDB_QF_ORDERED or 0 */
+  int32_t n_funcs;                   /* form A: 1..4; form B: 1 */
+  int32_t func[4];                   /* form A: SUM / COUNT / MAX / MIN; form B: any downsampling function */
+  int32_t agg_id[4];                 /* form A: RollupConfig id for the qualifier's first byte */
+} tsdbhip_preagg_spec;
+int tsdbhip_preagg_run(tsdbhip_ctx* ctx, const tsdbhip_preagg_spec* spec, int64_t* n_cells, uint64_t* qual_bytes,
+                       uint64_t* value_bytes);
+/* Copies the last preagg_run's cells to caller-allocated host arrays (any may be NULL):
+ * func_index[n_cells], group[n_cells] (batch group id), base_time[n_cells],
+ * qual_off[n_cells + 1], qualifier[qual_bytes], val_off[n_cells + 1], value[value_bytes]. */
+int tsdbhip_preagg_download(tsdbhip_ctx* ctx, int32_t* func_index, int32_t* group, uint32_t* base_time,
+                            uint64_t* qual_off, uint8_t* qualifier, uint64_t* val_off, uint8_t* value);
 
 /* ---- rollup read path ----------------------------------
  * A query over a rollup table (TsdbQuery with a RollupQuery, src/core/TsdbQuery.java:1293-1362;

@@ -195,6 +195,21 @@ class RollupSpec(C.Structure):
     ]
 
 
+class PreaggSpec(C.Structure):
+    """tsdbhip_preagg_spec: pre-aggregate (group-by rollup cell) generation."""
+    _fields_ = [
+        ("interval", RollupInterval),
+        ("ds_interval_ms", C.c_int64),
+        ("start_s", C.c_int64),
+        ("end_s", C.c_int64),
+        ("groupby_aggregator", C.c_int32),
+        ("flags", C.c_int32),
+        ("n_funcs", C.c_int32),
+        ("func", C.c_int32 * 4),
+        ("agg_id", C.c_int32 * 4),
+    ]
+
+
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,
               ds_all: bool = False, rate: bool = False, counter: bool = False,

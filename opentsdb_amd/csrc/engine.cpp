@@ -496,6 +496,19 @@ struct tsdbhip_ctx {
     uint64_t bytes = 0;
   } ro_out[4];
   int ro_n = 0;
+  // pre-aggregate generation (tsdbhip_preagg_run): the slab of the functions' group-by results,
+  // scratch, and the cells of the last run -- buffers of their own, so that a rollup_run result
+  // stays as it is
+  struct Preagg {
+    DevBuf val, flag, act, qerr, code, off, totals;   // slab [F][G][K], [F][G], [F]; [n + 1] codes / offsets
+    DevBuf o_func, o_group, o_base, o_qual, o_voff, o_val;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    hipEvent_t ev[3] = {};
+    int64_t cells = 0;
+    uint64_t qual_bytes = 0, value_bytes = 0;
+    int qlen = 3;
+  } pg;
   // rollup read path (tsdbhip_load_rollup): the resident batch holds the value series (batch
   // positions [0, ro_nval), their groups) and, with count cells, one count series per value
   // series (positions ro_nval + s, no group), both re-rowed into hour rows
@@ -818,6 +831,8 @@ static void release_batch(tsdbhip_ctx* c) {
   c->ro_nruns = 0;
   c->cmp_errs.clear();
   c->compact_ms = 0;
+  c->pg.cells = 0;   // (the pre-aggregate cells belong to the batch they came from)
+  c->pg.qual_bytes = c->pg.value_bytes = 0;
 }
 
 namespace tsdb {
@@ -857,6 +872,11 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   for (auto& o : c->ro_out)
     for (DevBuf* b : {&o.series, &o.base, &o.qual, &o.voff, &o.val}) b->release();
   if (c->ro_tmp) (void)hipFree(c->ro_tmp);
+  for (DevBuf* b : {&c->pg.val, &c->pg.flag, &c->pg.act, &c->pg.qerr, &c->pg.code, &c->pg.off, &c->pg.totals,
+                    &c->pg.o_func, &c->pg.o_group, &c->pg.o_base, &c->pg.o_qual, &c->pg.o_voff, &c->pg.o_val})
+    b->release();
+  if (c->pg.tmp) (void)hipFree(c->pg.tmp);
+  for (auto& e : c->pg.ev) if (e) (void)hipEventDestroy(e);
   if (c->cmp_tmp) (void)hipFree(c->cmp_tmp);
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
@@ -6370,6 +6390,197 @@ extern "C" int tsdbhip_rollup_download(tsdbhip_ctx* c, int32_t* series, uint32_t
     byte0 += o.bytes;
   }
   if (val_off) val_off[cell0] = byte0;
+  return 0;
+}
+
+// ---- pre-aggregate generation (tsdbhip.h): the group-by half of the rollup storage model ----
+// The n_funcs planned queries run through tsdbhip_run's device path one after the other; each
+// one's dense [G][K] rows, group activity and error word are copied device to device into the
+// slab (what collect() would download), then k_preagg.hip sizes, scans and writes every cell of
+// every function in one pass each.  The encode stage ends in ONE host synchronisation: the
+// output arrays are sized for the upper bound (every entry a float64 cell, 31 B an entry), so
+// the write kernel is queued before the totals are known.
+extern "C" int tsdbhip_preagg_run(tsdbhip_ctx* c, const tsdbhip_preagg_spec* sp, int64_t* n_cells,
+                                  uint64_t* qual_bytes, uint64_t* value_bytes) {
+  if (!c || !sp || !n_cells || !qual_bytes || !value_bytes) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_preagg_run");
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_preagg_run over a rollup batch (tsdbhip_load_rollup)");
+  const bool form_b = sp->interval.interval_s == 0;
+  if (!form_b && !iv_valid(&sp->interval)) return fail(TSDB_E_ILLEGAL_ARGUMENT, "invalid rollup interval");
+  if (sp->n_funcs < 1 || sp->n_funcs > (form_b ? 1 : 4))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, form_b ? "one downsampling function without a rollup interval"
+                                                : "1..4 rollup functions");
+  if (sp->start_s < 0 || sp->end_s <= sp->start_s) return fail(TSDB_E_ILLEGAL_ARGUMENT, "bad pre-aggregate time range");
+  if (sp->flags & ~TSDB_QF_ORDERED) return fail(TSDB_E_ILLEGAL_ARGUMENT, "unknown query flag");
+  if (sp->groupby_aggregator < 0 || sp->groupby_aggregator >= TSDB_AGG_COUNT_ALL ||
+      sp->groupby_aggregator == TSDB_AGG_NONE)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "Cannot write a group by data point without specifying the aggregation function");
+  for (int i = 0; i < sp->n_funcs; i++) {
+    const int f = sp->func[i];
+    if (form_b) {
+      if (f < 0 || f >= TSDB_AGG_COUNT_ALL || f == TSDB_AGG_NONE)
+        return fail(TSDB_E_ILLEGAL_ARGUMENT, "not a downsampling function");
+    } else if (f != TSDB_AGG_SUM && f != TSDB_AGG_COUNT && f != TSDB_AGG_MAX && f != TSDB_AGG_MIN) {
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "rollup functions are sum, count, max and min");
+    }
+  }
+  if (form_b && sp->ds_interval_ms <= 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "interval not > 0");
+  // addAggregatePointInternal takes second timestamps only (TSDB.java:1464)
+  if (form_b && sp->ds_interval_ms % 1000 != 0)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "bad timestamp: pre-aggregates take second timestamps, not a millisecond interval");
+  const int64_t interval_ms = form_b ? sp->ds_interval_ms : (int64_t)sp->interval.interval_s * 1000;
+  CtxLock lk(c);
+  HIP_OK(hipSetDevice(c->device));
+  auto& pg = c->pg;
+  pg.cells = 0;
+  pg.qual_bytes = pg.value_bytes = 0;
+  pg.qlen = form_b ? 2 : 3;
+  for (auto& e : pg.ev) if (!e) HIP_OK(hipEventCreate(&e));
+  const int64_t G = c->n_groups;
+  const int F = sp->n_funcs;
+  int64_t K = 0, B0 = 0, I = 0;
+  Plan Pacct;
+  HIP_OK(pg.qerr.ensure(4 * 4));
+  HIP_OK(hipEventRecord(pg.ev[0], c->stream));
+  for (int fi = 0; fi < F; fi++) {
+    tsdbhip_query q{};
+    q.start_time = sp->start_s;
+    q.end_time = sp->end_s - 1;
+    q.aggregator = sp->groupby_aggregator;
+    q.ds_function = sp->func[fi];
+    q.ds_fill = TSDB_FILL_NONE;
+    q.ds_interval_ms = interval_ms;
+    q.flags = sp->flags;
+    q.rate_counter_max = INT64_MAX;
+    Plan P;
+    int rc = plan_query(c, &q, P);
+    if (rc) return rc;
+    if (P.raw || P.none || P.anchored || P.mode != MODE_GRID)
+      return fail(TSDB_E_NOT_IMPLEMENTED, "pre-aggregates need a fixed epoch-aligned downsampling grid");
+    if (fi == 0) {
+      K = P.K;
+      B0 = P.B0;
+      I = P.I;
+      Pacct = P;
+      if ((double)F * (double)G * (double)K + 1.0 > 2147483647.0)
+        return fail(TSDB_E_NOT_IMPLEMENTED, "more than 2^31 pre-aggregate entries in one call");
+      const int64_t n = std::max<int64_t>(1, (int64_t)F * G * K);
+      HIP_OK(pg.val.ensure(n * 8));
+      HIP_OK(pg.flag.ensure(n));
+      HIP_OK(pg.act.ensure(std::max<int64_t>(1, (int64_t)F * G) * 4));
+    } else if (P.K != K || P.B0 != B0 || P.I != I) {
+      return fail(TSDB_E_NOT_IMPLEMENTED, "pre-aggregate functions planned on different grids");
+    }
+    // what tsdbhip_run launches for this query
+    if (P.gsel || P.ordered) {
+      rc = P.gsel ? run_sel_group(c, &q, P, G) : run_ordered(c, &q, P, G);
+    } else {
+      P.seq_dense = seq_dense_wanted(c, P);
+      rc = run_device(c, &q, P, G, true);
+    }
+    if (rc) return rc;
+    const int64_t gk = G * K;
+    if (gk) {
+      HIP_OK(hipMemcpyAsync(pg.val.as<double>() + fi * gk, c->out_val.p, gk * 8, hipMemcpyDeviceToDevice, c->stream));
+      HIP_OK(hipMemcpyAsync(pg.flag.as<uint8_t>() + fi * gk, c->out_flag.p, gk, hipMemcpyDeviceToDevice, c->stream));
+      HIP_OK(hipMemcpyAsync(pg.act.as<uint32_t>() + fi * G, c->gact.p, G * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_OK(hipMemcpyAsync(pg.qerr.as<int32_t>() + fi, c->err.p, 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIP_OK(hipEventRecord(pg.ev[1], c->stream));
+  // encode: size, scan, write over all F * G * K entries (+ the sentinel)
+  const int64_t n = (int64_t)F * G * K;
+  HIP_OK(pg.code.ensure(n + 1));
+  HIP_OK(pg.off.ensure((n + 1) * 8));
+  HIP_OK(pg.totals.ensure(sizeof(PreaggTotals)));
+  HIP_OK(pg.o_func.ensure(std::max<int64_t>(1, n) * 4));
+  HIP_OK(pg.o_group.ensure(std::max<int64_t>(1, n) * 4));
+  HIP_OK(pg.o_base.ensure(std::max<int64_t>(1, n) * 4));
+  HIP_OK(pg.o_qual.ensure(std::max<int64_t>(1, n) * pg.qlen));
+  HIP_OK(pg.o_voff.ensure((n + 1) * 8));
+  HIP_OK(pg.o_val.ensure(std::max<int64_t>(1, n) * 8));
+  HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
+  PreaggParams pp{};
+  pp.val = pg.val.as<double>();
+  pp.flag = pg.flag.as<uint8_t>();
+  pp.act = pg.act.as<uint32_t>();
+  pp.qerr = pg.qerr.as<int32_t>();
+  pp.n = n;
+  pp.G = G;
+  pp.K = K;
+  pp.B0 = B0;
+  pp.I = I;
+  pp.n_funcs = F;
+  pp.form_b = form_b ? 1 : 0;
+  if (!form_b) pp.iv = to_iv(&sp->interval);
+  for (int i = 0; i < F; i++) pp.agg_id[i] = sp->agg_id[i];
+  pp.code = pg.code.as<uint8_t>();
+  pp.off = pg.off.as<uint64_t>();
+  pp.o_func = pg.o_func.as<int32_t>();
+  pp.o_group = pg.o_group.as<int32_t>();
+  pp.o_base = pg.o_base.as<uint32_t>();
+  pp.o_qual = pg.o_qual.as<uint8_t>();
+  pp.o_voff = pg.o_voff.as<uint64_t>();
+  pp.o_val = pg.o_val.as<uint8_t>();
+  pp.err = c->err.as<int32_t>();
+  pp.totals = pg.totals.as<PreaggTotals>();
+  HIP_OK(launch_preagg_size(pp, c->stream));
+  HIP_OK(preagg_scan(pp.code, pg.off.as<uint64_t>(), n + 1, &pg.tmp, &pg.tmp_bytes, c->stream));
+  HIP_OK(launch_preagg_write(pp, c->stream));
+  HIP_OK(hipEventRecord(pg.ev[2], c->stream));
+  HIP_OK(c->h_small.ensure(sizeof(PreaggTotals)));
+  auto* tot = reinterpret_cast<PreaggTotals*>(c->h_small.p);
+  HIP_OK(hipMemcpyAsync(tot, pg.totals.p, sizeof(PreaggTotals), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  {
+    float t01 = 0, t12 = 0;
+    (void)hipEventElapsedTime(&t01, pg.ev[0], pg.ev[1]);
+    (void)hipEventElapsedTime(&t12, pg.ev[1], pg.ev[2]);
+    c->timing.decode_downsample_ms = t01;   // the functions' input passes and slab copies
+    c->timing.group_reduce_ms = t12;        // the encode stage: size + scan + write
+    c->timing.total_ms = t01 + t12;
+    c->timing.fast_ms = 0;
+    c->timing.fused_queries = 0;
+    account(c, Pacct);
+  }
+  int32_t err = tot->err;
+  // an infinite value trips AggregationIterator's Inf check (IllegalStateException) in the
+  // query; for a pre-aggregate it is addAggregatePoint's rejection
+  if (err == TSDB_E_ILLEGAL_STATE) err = TSDB_E_ILLEGAL_ARGUMENT;
+  if (err) return fail(err, "pre-aggregate generation: error raised by the device path, or a NaN / infinite value "
+                            "(addAggregatePoint rejects it)");
+  pg.cells = tot->cells;
+  pg.qual_bytes = tot->qual_bytes;
+  pg.value_bytes = tot->value_bytes;
+  *n_cells = pg.cells;
+  *qual_bytes = pg.qual_bytes;
+  *value_bytes = pg.value_bytes;
+  return 0;
+}
+
+// Copies the last preagg_run's cells to caller-allocated host arrays (any may be null).
+extern "C" int tsdbhip_preagg_download(tsdbhip_ctx* c, int32_t* func_index, int32_t* group, uint32_t* base_time,
+                                       uint64_t* qual_off, uint8_t* qualifier, uint64_t* val_off, uint8_t* value) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  MD_REFUSE(c, "tsdbhip_preagg_download");
+  CtxLock lk(c);
+  HIP_OK(hipSetDevice(c->device));
+  const auto& pg = c->pg;
+  const int64_t n = pg.cells;
+  if (n) {
+    if (func_index) HIP_OK(hipMemcpyAsync(func_index, pg.o_func.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (group) HIP_OK(hipMemcpyAsync(group, pg.o_group.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (base_time) HIP_OK(hipMemcpyAsync(base_time, pg.o_base.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (qualifier) HIP_OK(hipMemcpyAsync(qualifier, pg.o_qual.p, pg.qual_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (val_off) HIP_OK(hipMemcpyAsync(val_off, pg.o_voff.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (value && pg.value_bytes)
+      HIP_OK(hipMemcpyAsync(value, pg.o_val.p, pg.value_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+  } else if (val_off) {
+    val_off[0] = 0;
+  }
+  if (qual_off)
+    for (int64_t i = 0; i <= n; i++) qual_off[i] = (uint64_t)i * pg.qlen;
   return 0;
 }
 

@@ -451,6 +451,39 @@ struct RollupAggParams {
   uint8_t* pres;
 };
 hipError_t launch_rollup_agg(const GridParams& p, const RollupAggParams& rp, hipStream_t s);
+
+// pre-aggregate generation (k_preagg.hip): the slab of n_funcs group-by results, dense
+// [n_funcs][G][K], entry idx = (f * G + g) * K + k.  Entry n (one past the last) is a sentinel
+// whose scanned offset holds the totals.
+struct PreaggTotals {
+  int64_t cells;
+  uint64_t qual_bytes, value_bytes;
+  int32_t err, pad;
+};
+struct PreaggParams {
+  const double* val;        // [n] group-by values
+  const uint8_t* flag;      // [n] emit flags (k_emit / k_sel_seg / k_ordered)
+  const uint32_t* act;      // [n_funcs * G] the group has a span in the scan range
+  const int32_t* qerr;      // [n_funcs] error word each function's query left
+  int64_t n, G, K, B0, I;   // slot k is timestamp B0 + k * I (ms)
+  int32_t n_funcs;
+  int32_t form_b;           // 0: rollup qualifier (3 bytes), 1: Internal.buildQualifier (2 bytes)
+  RollupIv iv;
+  int32_t agg_id[4];
+  uint8_t* code;            // [n + 1] 0: no cell, else the value length (4 / 8)
+  const uint64_t* off;      // [n + 1] exclusive scan: cells (low 32 bits), float64 cells (high)
+  int32_t* o_func;
+  int32_t* o_group;
+  uint32_t* o_base;
+  uint8_t* o_qual;          // 3 (2) bytes a cell
+  uint64_t* o_voff;         // [cells + 1]
+  uint8_t* o_val;
+  int32_t* err;
+  PreaggTotals* totals;
+};
+hipError_t launch_preagg_size(const PreaggParams& p, hipStream_t s);
+hipError_t preagg_scan(const uint8_t* code, uint64_t* off, int64_t n1, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_preagg_write(const PreaggParams& p, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

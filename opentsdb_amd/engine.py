@@ -34,7 +34,7 @@ EXPORTS = [
     "tsdbhip_hist_run_range", "tsdbhip_hist_result_free", "tsdbhip_expr_map", "tsdbhip_expr_zip", "tsdbhip_expr_topn",
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
-    "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option",
+    "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -145,6 +145,9 @@ def lib():
                                                C.POINTER(abi.RollupInterval), C.c_void_p]
         L.tsdbhip_rollup_run.argtypes = [vp, C.POINTER(abi.RollupSpec), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
         L.tsdbhip_rollup_download.argtypes = [vp] + [C.c_void_p] * 5
+        L.tsdbhip_preagg_run.argtypes = [vp, C.POINTER(abi.PreaggSpec), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]
+        L.tsdbhip_preagg_download.argtypes = [vp] + [C.c_void_p] * 7
         L.tsdbhip_debug_rows.argtypes = [vp] + [C.c_void_p] * 4
         L.tsdbhip_debug_index.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int)]
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
@@ -271,6 +274,28 @@ class RollupCells:
     def cell(self, i):
         """(series, base_time, qualifier bytes, value bytes) of cell i."""
         return (int(self.series[i]), int(self.base_time[i]), bytes(self.qualifier[i]),
+                bytes(self.value[self.val_off[i]:self.val_off[i + 1]]))
+
+
+class PreaggCells:
+    """Cells of one pre-aggregate generation, in (function, group, time) order."""
+
+    def __init__(self, func_index, group, base_time, qual_off, qualifier, val_off, value):
+        self.func_index = func_index  # int32 [n] index into the spec's functions
+        self.group = group            # int32 [n] batch group id
+        self.base_time = base_time    # uint32 [n] row base time (s)
+        self.qual_off = qual_off      # uint64 [n + 1]
+        self.qualifier = qualifier    # uint8 [qual_off[-1]]: 3 bytes a cell (rollup interval) or 2
+        self.val_off = val_off        # uint64 [n + 1]
+        self.value = value            # uint8 [val_off[-1]]
+
+    def __len__(self):
+        return len(self.group)
+
+    def cell(self, i):
+        """(func_index, group, base_time, qualifier bytes, value bytes) of cell i."""
+        return (int(self.func_index[i]), int(self.group[i]), int(self.base_time[i]),
+                bytes(self.qualifier[self.qual_off[i]:self.qual_off[i + 1]]),
                 bytes(self.value[self.val_off[i]:self.val_off[i + 1]]))
 
 
@@ -527,6 +552,49 @@ class Engine:
     def rollup(self, interval: abi.RollupInterval, start_s: int, end_s: int,
                funcs=(("sum", 0), ("count", 1), ("max", 2), ("min", 3))) -> RollupCells:
         return self.rollup_download(*self.rollup_run(interval, start_s, end_s, funcs))
+
+    # ---- pre-aggregate generation (tsdbhip_preagg_run) ----
+    def preagg_run(self, interval, start_s: int, end_s: int, groupby_aggregator="sum",
+                   funcs=(("sum", 0), ("count", 1), ("max", 2), ("min", 3)), flags: int = 0, ds_interval_ms: int = 0):
+        """Generates the pre-aggregate (group-by) cells of the resident batch on the device;
+        returns (n_cells, qual_bytes, value_bytes).  interval: a RollupInterval -> the cells of
+        its group-by table, funcs = [(rollup function, rollup aggregator id)]; None -> the default
+        interval's group-by table at ds_interval_ms, funcs = [(downsampling function, ignored)]."""
+        sp = abi.PreaggSpec()
+        if interval is not None:
+            sp.interval = interval
+        sp.ds_interval_ms = ds_interval_ms
+        sp.start_s = start_s
+        sp.end_s = end_s
+        sp.groupby_aggregator = (abi.AGG[groupby_aggregator] if isinstance(groupby_aggregator, str)
+                                 else groupby_aggregator)
+        sp.flags = flags
+        sp.n_funcs = len(funcs)
+        for i, (fn, aid) in enumerate(funcs[:4]):
+            sp.func[i] = abi.AGG[fn] if isinstance(fn, str) else fn
+            sp.agg_id[i] = aid
+        n, qb, vb = C.c_int64(), C.c_uint64(), C.c_uint64()
+        _check(lib().tsdbhip_preagg_run(self.ctx, C.byref(sp), C.byref(n), C.byref(qb), C.byref(vb)))
+        return n.value, qb.value, vb.value
+
+    def preagg_download(self, n_cells: int, qual_bytes: int, value_bytes: int) -> PreaggCells:
+        fi = np.zeros(max(1, n_cells), np.int32)
+        grp = np.zeros(max(1, n_cells), np.int32)
+        base = np.zeros(max(1, n_cells), np.uint32)
+        qoff = np.zeros(n_cells + 1, np.uint64)
+        qual = np.zeros(max(1, qual_bytes), np.uint8)
+        voff = np.zeros(n_cells + 1, np.uint64)
+        val = np.zeros(max(1, value_bytes), np.uint8)
+        _check(lib().tsdbhip_preagg_download(self.ctx, fi.ctypes.data, grp.ctypes.data, base.ctypes.data,
+                                             qoff.ctypes.data, qual.ctypes.data, voff.ctypes.data, val.ctypes.data))
+        return PreaggCells(fi[:n_cells], grp[:n_cells], base[:n_cells], qoff, qual[:qual_bytes], voff,
+                           val[:value_bytes])
+
+    def preagg(self, interval, start_s: int, end_s: int, groupby_aggregator="sum",
+               funcs=(("sum", 0), ("count", 1), ("max", 2), ("min", 3)), flags: int = 0,
+               ds_interval_ms: int = 0) -> PreaggCells:
+        return self.preagg_download(*self.preagg_run(interval, start_s, end_s, groupby_aggregator, funcs, flags,
+                                                     ds_interval_ms))
 
     # ---- multi-GPU exchange (see include/tsdbhip.h and opentsdb_amd/dist.py) ----
     def partials_layout(self, q: abi.Query, n_groups_global: int) -> abi.PartialsLayout:

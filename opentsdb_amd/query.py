@@ -213,6 +213,30 @@ class TsdbQuery:
         self.downsampler: DownsamplingSpecification | None = None
         self.flags = 0
         self.rollup_usage = "ROLLUP_NOFALLBACK"   # TsdbQuery.java:150
+        self.pre_aggregate = False                # TsdbQuery.java:154
+
+    def setPreAggregate(self, pre_aggregate: bool = True):
+        """TSSubQuery.setPreAggregate -> TsdbQuery.pre_aggregate (TsdbQuery.java:458): read the
+        pre-aggregated (group-by) table instead of aggregating after the fetch."""
+        self.pre_aggregate = bool(pre_aggregate)
+
+    def isPreAggregate(self) -> bool:   # TsdbQuery.java:257-259
+        return self.pre_aggregate
+
+    def _agg_tag(self):
+        """(tsdb.getAggTagKey(), tsdb.getRawTagValue()): tsd.rollups.agg_tag_key / raw_agg_tag_value."""
+        if self.rollups is not None:
+            return self.rollups.agg_tag_key, self.rollups.raw_agg_tag_value
+        return "_aggregate", "RAW"
+
+    def tableToBeScanned(self):
+        """TsdbQuery.tableToBeScanned (:1484-1503) as (kind, rollup interval name | None):
+        "rollup-agg" the matched interval's group-by table, "rollup" its temporal table, "agg" the
+        default interval's group-by table, "raw" the data table."""
+        name = self.rollup_interval_name()
+        if name is not None:
+            return ("rollup-agg" if self.pre_aggregate else "rollup"), name
+        return ("agg" if self.pre_aggregate else "raw"), None
 
     def setRollupUsage(self, usage: str | None):
         """TSSubQuery.setRollupUsage / ROLLUP_USAGE.parse (TsdbQuery.java:207-222): an unknown
@@ -254,6 +278,12 @@ class TsdbQuery:
         self.aggregator = function
         self.rate = rate
         self.rate_options = rate_options or RateOptions()
+        # a literal filter on the aggregate tag key asking for anything but the raw value reads
+        # pre-aggregated data (TsdbQuery.java:565-571)
+        agg_tag_key, raw_value = self._agg_tag()
+        v = self.tags.get(agg_tag_key)
+        if v is not None and "*" not in v and v != raw_value:
+            self.pre_aggregate = True
 
     def downsample(self, interval, function: str | None = None, fill_policy: str = "none"):
         """downsample(interval_ms, Aggregator[, FillPolicy]) or downsample("1m-avg")."""
@@ -377,9 +407,20 @@ class TsdbQuery:
         if f is None:
             spans, need_count = [], False
         else:
-            spans, need_count = self.rollups.scan_cells(name, self.metric, ds.function, self.aggregator, f[0])
+            spans, need_count = self.rollups.scan_cells(name, self.metric, ds.function, self.aggregator, f[0],
+                                                        groupby=self.pre_aggregate)
         keys, gids = self._groups(spans, f[1] if f else [])
         return make_rollup_batch(spans, gids, iv, need_count, self.fix_duplicates), keys
+
+    def _data_store(self):
+        """The table a query without a rollup match scans (tableToBeScanned :1495-1500): the data
+        table, or for a pre-aggregate query the default interval's group-by table -- ordinary
+        datapoint columns, so the ordinary batch path reads it."""
+        if not self.pre_aggregate:
+            return self.store
+        if self.rollups is None:
+            raise ValueError("a pre-aggregate query needs a rollup config (the default interval's group-by table)")
+        return self.rollups.default_groupby
 
     def build_batch(self):
         """findSpans + GroupByAndAggregateCB grouping (TsdbQuery.java:795-1049).
@@ -415,7 +456,7 @@ class TsdbQuery:
                     return False
             return True
 
-        spans = self.store.scan(self.metric, s, e, pred)
+        spans = self._data_store().scan(self.metric, s, e, pred)
         if not group_bys:
             keys = [()]
             gids = [0] * len(spans)

@@ -9,7 +9,10 @@ The reference keeps this above the aggregation path, and so does this mirror:
     (src/core/TSDB.java:1322-1588): one cell per (row key, aggregator, timestamp) with the
     qualifier [aggregator id][offset << 4 | flags] (RollupUtils.buildRollupQualifier
     :143-171), or an old "<agg>:" string prefix; a row key's cells come back from a scan in
-    qualifier byte order, one version per qualifier;
+    qualifier byte order, one version per qualifier; every interval has a temporal table and a
+    group-by table (pre-aggregates, is_groupby: series tagged _aggregate=<AGGREGATOR>), and the
+    default interval a group-by table of ordinary datapoint columns; put_preagg_cells() stores
+    the cells Engine.preagg generated on the GPU;
   * scan_cells() -- TsdbQuery's rollup scan (src/core/TsdbQuery.java:1415-1460: the
     qualifier filter of the rollup aggregator, or of sum and count for avg) and
     RollupSeq.setRow / addRow's classification of each cell as the aggregate's value or a
@@ -83,16 +86,61 @@ def normalize_agg(agg: str) -> str:
 
 
 class RollupStore:
-    """Rollup tables keyed by interval name; uids shared with a raw MockStore."""
+    """Rollup tables keyed by interval name; uids shared with a raw MockStore.  Every interval
+    has a temporal table (RollupInterval.getTemporalTable: one series' buckets) and a group-by
+    table (getGroupbyTable: pre-aggregates, series tagged <agg_tag_key>=<AGGREGATOR>); the default
+    interval's group-by table holds ordinary datapoint columns (TSDB.java:1531-1535,1560) and is
+    a MockStore.  tag_raw / agg_tag_key / raw_agg_tag_value / block_derived:
+    tsd.rollups.tag_raw, .agg_tag_key, .raw_agg_tag_value, .block_derived (Config.java:576-579)."""
 
-    def __init__(self, config: RollupConfig, raw: MockStore | None = None):
+    def __init__(self, config: RollupConfig, raw: MockStore | None = None, tag_raw: bool = False,
+                 agg_tag_key: str = "_aggregate", raw_agg_tag_value: str = "RAW", block_derived: bool = True):
         self.config = config
         self.raw = raw if raw is not None else MockStore()
         self.tables = {name: {} for name in config.intervals}   # name -> {(m, tags, base): {qual: value}}
+        self.groupby_tables = {name: {} for name in config.intervals}
+        self.default_groupby = MockStore(self.raw.fix_duplicates)
+        self.default_groupby.metrics = self.raw.metrics   # one UniqueId set per TSD
+        self.default_groupby.tagk = self.raw.tagk
+        self.default_groupby.tagv = self.raw.tagv
+        self.tag_raw = tag_raw
+        self.agg_tag_key = agg_tag_key
+        self.raw_agg_tag_value = raw_agg_tag_value
+        self.block_derived = block_derived
 
-    # TSDB.addAggregatePoint (long / float / double overloads) :1322-1440
-    def add_aggregate_point(self, metric: str, ts: int, value, tags: dict, interval: str, aggregator: str,
-                            kind: str | None = None):
+    def _table(self, interval: str, groupby: bool = False):
+        return (self.groupby_tables if groupby else self.tables)[interval]
+
+    def _aggregate_tag(self, tags: dict, is_groupby: bool, groupby_aggregator, metric: str):
+        """The aggregate-tag logic and the group-by aggregator checks of addAggregatePointInternal
+        (TSDB.java:1471-1512); `tags` is updated in place, as the reference updates its map."""
+        agg_tag_value = tags.get(self.agg_tag_key)
+        if agg_tag_value is None:
+            if not is_groupby:   # a rollup on "raw" data
+                if self.tag_raw:
+                    tags[self.agg_tag_key] = self.raw_agg_tag_value
+                agg_tag_value = self.raw_agg_tag_value
+            else:                # pre-aggregated: the aggregator is the tag
+                agg_tag_value = groupby_aggregator.upper()
+                tags[self.agg_tag_key] = agg_tag_value
+        else:
+            if groupby_aggregator is None or agg_tag_value.lower() != groupby_aggregator.lower():
+                raise ValueError(f"Given tag value for {self.agg_tag_key} of {agg_tag_value} did not match the "
+                                 f"group by aggregator of {groupby_aggregator} for {metric} {tags}")
+            agg_tag_value = groupby_aggregator.upper()
+            tags[self.agg_tag_key] = agg_tag_value
+        if is_groupby:
+            if groupby_aggregator.lower() not in abi.AGG:   # Aggregators.get on the lower-cased name
+                raise ValueError(f"Invalid group by aggregator {groupby_aggregator} with metric {metric} {tags}")
+            if self.block_derived and agg_tag_value in ("AVG", "DEV"):
+                raise ValueError(f"Derived group by aggregations are not allowed {groupby_aggregator} "
+                                 f"with metric {metric} {tags}")
+
+    # TSDB.addAggregatePoint (long / float / double overloads) :1322-1440 -> addAggregatePointInternal
+    # :1441-1588, its checks in the reference's order
+    def add_aggregate_point(self, metric: str, ts: int, value, tags: dict, interval: str | None,
+                            aggregator: str | None, kind: str | None = None, is_groupby: bool = False,
+                            groupby_aggregator: str | None = None):
         if kind is None:
             kind = "long" if isinstance(value, int) else "float"
         if kind == "long":
@@ -101,33 +149,82 @@ class RollupStore:
             if value != value or value in (float("inf"), float("-inf")):
                 raise ValueError(f"value is NaN or Infinite: {value}")
             v, flags = (struct.pack(">f", value), 0x8 | 0x3) if kind == "float" else (struct.pack(">d", value), 0x8 | 0x7)
+        if is_groupby and not groupby_aggregator:   # :1455-1460
+            raise ValueError("Cannot write a group by data point without specifying the aggregation function. "
+                             f"Metric={metric} tags={tags}")
         if ts < 0 or (ts & SECOND_MASK) != 0:   # :1463-1469: rollups take seconds only
             raise ValueError(f"{'negative' if ts < 0 else 'bad'} timestamp={ts}")
+        self._aggregate_tag(tags, is_groupby, groupby_aggregator, metric)
         from . import engine
-        iv = self.config.intervals[interval]
-        agg_id = self.config.getIdForAggregator(aggregator)
+        if interval:   # :1516-1530
+            if interval not in self.config.intervals:
+                raise NoSuchRollupForIntervalException(interval)
+            iv = self.config.intervals[interval]
+            agg_id = self.config.getIdForAggregator(aggregator)
+        if aggregator is not None and self.block_derived and aggregator.upper() in ("AVG", "DEV"):
+            raise ValueError(f"Derived rollup aggregations are not allowed {aggregator.upper()} with metric {metric} {tags}")
+        if not interval:   # :1531-1535, 1555-1561: the default interval's group-by table
+            if not is_groupby:
+                raise ValueError("Interval cannot be null for a non-group by point")
+            self.default_groupby._put(metric, ts, v, flags, tags)
+            return
         base = engine.rollup_basetime(ts, iv)
         qual = engine.rollup_qualifier(ts, base, flags, agg_id, iv)
         m, t = self.raw._series_uids(metric, tags)
-        self.tables[interval].setdefault((m, t, base), {})[qual] = v
+        self._table(interval, is_groupby).setdefault((m, t, base), {})[qual] = v
+
+    def put_preagg_cells(self, metric: str, keys, group_by_tagks, cells, interval_name: str | None,
+                         groupby_aggregator: str):
+        """Stores the cells of Engine.preagg (a PreaggCells) as a TSD job would with
+        addAggregatePoint(metric, ts, value, tags, true, interval, rollup_agg, groupby_agg): the
+        series of group g carries the group's tag values -- keys[g], the tag value uids of
+        group_by_tagks in tag key uid order, as TsdbQuery.build_batch returns them -- plus the
+        aggregate tag.  interval_name None: the default interval's group-by table (cells of form
+        B, 2-byte qualifiers); else that interval's group-by table (3-byte rollup qualifiers)."""
+        from .store import _Row
+        if interval_name and interval_name not in self.config.intervals:
+            raise NoSuchRollupForIntervalException(interval_name)
+        tagk_ids = self.raw.tagk.ids
+        tagks = sorted(group_by_tagks, key=lambda k: tagk_ids[k])
+        tagv_names = {u: n for n, u in self.raw.tagv.ids.items()}
+        uids = {}
+        for g in sorted({int(x) for x in cells.group}):
+            tags = {k: tagv_names[u] for k, u in zip(tagks, keys[g])}
+            self._aggregate_tag(tags, True, groupby_aggregator, metric)
+            uids[g] = self.raw._series_uids(metric, tags)
+        for i in range(len(cells)):
+            _, g, base, qual, val = cells.cell(i)
+            m, t = uids[g]
+            if interval_name:
+                self.groupby_tables[interval_name].setdefault((m, t, base), {})[qual] = val
+            else:
+                row = self.default_groupby.rows.setdefault((m, t, base), _Row())
+                row.cells[qual] = val
+                if qual in row.order:
+                    row.order.remove(qual)
+                row.order.append(qual)
 
     def add_column(self, interval: str, metric: str, tags: dict, base: int, qualifier: bytes, value: bytes):
         """A raw cell (e.g. the old "sum:" string-prefixed qualifier, TestTsdbQueryRollup.oldStringPrefix)."""
         m, t = self.raw._series_uids(metric, tags)
         self.tables[interval].setdefault((m, t, base), {})[bytes(qualifier)] = bytes(value)
 
-    def series(self, interval: str, metric: str):
+    def series(self, interval: str, metric: str, groupby: bool = False):
         m = self.raw.metrics.ids.get(metric)
         if m is None:
             return []
         from .store import _tag_bytes
-        return sorted({(k[0], k[1]) for k in self.tables[interval] if k[0] == m}, key=lambda k: _tag_bytes(k[1]))
+        return sorted({(k[0], k[1]) for k in self._table(interval, groupby) if k[0] == m},
+                      key=lambda k: _tag_bytes(k[1]))
 
-    def scan_cells(self, interval: str, metric: str, ds_function: str, group_by: str, tag_pred=None):
+    def scan_cells(self, interval: str, metric: str, ds_function: str, group_by: str, tag_pred=None,
+                   groupby: bool = False):
         """The scan of a rollup query (TsdbQuery.java:1415-1460) and RollupSeq's cell
         classification (RollupSeq.java:122-230).  Returns [(series_key, [(base, values,
         counts)])] in row key order, values / counts lists of (2-byte qualifier, value
-        bytes), and whether the query reads counts (RollupSeq.need_count)."""
+        bytes), and whether the query reads counts (RollupSeq.need_count).  groupby: scan the
+        interval's group-by table (a pre-aggregate query, TsdbQuery.tableToBeScanned :1484-1503)."""
+        table = self._table(interval, groupby)
         rollup_agg = normalize_agg(ds_function)
         gb = normalize_agg(group_by)
         need_count = gb in ("avg", "dev")
@@ -146,12 +243,12 @@ class RollupStore:
             count_id = None
             agg_prefix = (gb + ":").encode()   # RollupQuery.getRollupAggPrefix (the group-by's name)
         out = []
-        for sk in self.series(interval, metric):
+        for sk in self.series(interval, metric, groupby):
             if tag_pred is not None and not tag_pred(sk[1]):
                 continue
             rows = []
-            for base in sorted(b for (m, t, b) in self.tables[interval] if (m, t) == sk):
-                cells = self.tables[interval][(sk[0], sk[1], base)]
+            for base in sorted(b for (m, t, b) in table if (m, t) == sk):
+                cells = table[(sk[0], sk[1], base)]
                 vals, cnts = [], []
                 for q in sorted(cells):   # HBase returns a row's columns in qualifier order
                     if not any(q.startswith(p) for p in prefixes):
