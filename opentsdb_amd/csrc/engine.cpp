@@ -3452,6 +3452,7 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
     int32_t* r1[2] = {c->r1a.as<int32_t>(), c->r1b.as<int32_t>()};
     int32_t* r3[2] = {c->r3a.as<int32_t>(), c->r3b.as<int32_t>()};
     int64_t routed = 0;   // tiles of host lists sent straight to k_grid
+    const int32_t* none_final = rn + 2;
     if (none) {
       // NONE aggregator: one tile per series (not the group tiles the lists index) --
       // class A over every tile, class B over what A handed back
@@ -3463,6 +3464,7 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
       if (rc == 1) {
         if (a) to_grid.push_back({r1[0], {rn + 0, nt}});
         else return fail(TSDB_E_HIP, "no fast class ran");   // unreachable: `fast` needs one
+        none_final = rn + 0;   // no class B: what A handed back is what k_grid redoes (timing.redo_tiles)
       }
     }
     for (int cls = 0; cls < 2 && !none; cls++) {
@@ -3538,7 +3540,7 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
       g2.n_launch = tg.second.second;
       HIP_OK(launch_grid(g2, P.f, c->stream));
     }
-    c->redo_final = rn + 2;
+    c->redo_final = none ? none_final : rn + 2;
     c->redo_other = none ? 0 : (int64_t)c->tl_other.size() + routed;
   } else {
     HIP_OK(launch_grid(gp, P.f, c->stream));

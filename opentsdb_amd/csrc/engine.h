@@ -42,11 +42,30 @@ enum : uint32_t {
   ROW_NOCERT = 0x1000000,   // two of the row's values cannot add exactly (row_nocert): an order-free sum is ruled out
 };
 
-// The exactness certificate (n * absmax <= 2^(52 + lsb)) fails for any bucket of
-// two or more of this row's values: sums over them must keep Java's order (k_grid's sequential path).
+// The exactness certificate, the one statement of its inequality: n values, each
+// a multiple of 2^L and at most A in magnitude, add to the same bits in any order when
+// n * A <= 2^(52 + L) --
+// and n * A is finite.  The overflow case is explicit: for 52 + L > 1023 the threshold is no
+// double (ldexp gives +inf, and inf <= inf would hold); there every finite n * A is below it, and
+// an n * A that is not finite never certifies (partial sums could reach +-Inf in one order and
+// cancel in another).  Callers pass L and A of what is summed (squareSum: 2 * lsb, absmax^2).
+// It holds down to the subnormals: for L >= -1074 every summand is a multiple of 2^L that a double
+// holds; for a squareSum's L = 2 * lsb below that, A <= 2^(52 + L) / n < 2^-1022 makes every square
+// and every partial sum a subnormal, and subnormals add exactly.  So row_nocert and k_grid's two
+// sites use it as it stands.  The streaming kernels (fast_cert, kcommon.h) decline L < -1022 on
+// top of it: they fold buckets with LDS floating-point atomics, which are not relied on to keep
+// subnormal operands; that is a premise of those kernels, not part of the certificate.
+__host__ __device__ inline bool sum_cert(double n, int L, double A) {
+  const double na = n * A * (1.0 + 1e-12);
+  if (!(na < INFINITY)) return false;   // A infinite or NaN, or n * A overflows
+  return 52 + L > 1023 || na <= ldexp(1.0, 52 + L);
+}
+
+// The certificate fails for any bucket of two or more of this row's values: sums over them must
+// keep Java's order (k_grid's sequential path).
 __host__ __device__ inline bool row_nocert(int lsb, double absmax) {
   if (lsb == INT32_MAX || absmax == 0.0) return false;
-  return isinf(absmax) || 2.0 * absmax * (1.0 + 1e-12) > ldexp(1.0, 52 + lsb);
+  return !sum_cert(2.0, lsb, absmax);
 }
 
 // A rollup value row with its lock-step count row, packed once per rollup batch (k_ro_pack) for

@@ -500,7 +500,7 @@ __device__ __forceinline__ void rf_chunk(const GridParams& p, const RfLds& L, Rf
           rf_flush<VL>(L, A);
           A.slot = s0;
         }
-        A.n += nv0;
+        A.n += min(nv0, CH);   // (nv0 counts the row's datapoints from this chunk's start on)
         // a chunk whose lanes are all full or empty (rows of a multiple of 8 datapoints, e.g.
         // 360) takes the unmasked loop on its full lanes
         const bool whole = FULL || __all(nvl == 0 || nvl == DPL);

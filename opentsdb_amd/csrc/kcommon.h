@@ -1486,7 +1486,7 @@ __global__ __launch_bounds__(256) void k_grid(GridParams p) {
         if (needs_cert<F>() && !force_slow && cd.lsb != INT32_MAX && cd.absmax != 0.0) {
           const int L = (F == F_SQUARESUM) ? 2 * cd.lsb : cd.lsb;
           const double A = (F == F_SQUARESUM) ? cd.absmax * cd.absmax : cd.absmax;
-          seq = isinf(A) || 2.0 * A * (1.0 + 1e-12) > ldexp(1.0, 52 + L);   // (row_nocert for sums)
+          seq = !sum_cert(2.0, L, A);   // (row_nocert for sums)
         }
       }
     }
@@ -1529,8 +1529,7 @@ __global__ __launch_bounds__(256) void k_grid(GridParams p) {
           // all partial sums exactly representable => any association order == Java's order
           const int L = (F == F_SQUARESUM) ? 2 * lsb : lsb;
           const double A = (F == F_SQUARESUM) ? amax * amax : amax;
-          const bool ok = (A == 0.0) ||
-                          (lsb != INT32_MAX && !isinf(A) && (double)st.nmax * A * (1.0 + 1e-12) <= ldexp(1.0, 52 + L));
+          const bool ok = (A == 0.0) || (lsb != INT32_MAX && sum_cert((double)st.nmax, L, A));
           slow = !ok;
         }
       }
@@ -2012,8 +2011,7 @@ __device__ __forceinline__ bool fast_cert(uint32_t nmax, int lsb, double amax) {
   if (!needs_cert<F>()) return true;
   const int Lb = (F == F_SQUARESUM) ? 2 * lsb : lsb;
   const double A = (F == F_SQUARESUM) ? amax * amax : amax;
-  return (A == 0.0) || (lsb != INT32_MAX && Lb >= -1022 && !isinf(A) &&
-                        (double)nmax * A * (1.0 + 1e-12) <= ldexp(1.0, 52 + Lb));
+  return (A == 0.0) || (lsb != INT32_MAX && Lb >= -1022 && sum_cert((double)nmax, Lb, A));
 }
 
 template <int F>
@@ -2089,13 +2087,7 @@ __device__ __forceinline__ bool fast_series_end(const GridParams& p, const FastL
     L.acc[k] = v;
   }
   nmax = (uint32_t)wave_max((int)nmax);
-  if (needs_cert<F>()) {
-    const int Lb = (F == F_SQUARESUM) ? 2 * lsb : lsb;
-    const double A = (F == F_SQUARESUM) ? amax * amax : amax;
-    const bool ok = (A == 0.0) || (lsb != INT32_MAX && Lb >= -1022 && !isinf(A) &&
-                                   (double)nmax * A * (1.0 + 1e-12) <= ldexp(1.0, 52 + Lb));
-    if (!ok) return false;
-  }
+  if (!fast_cert<F>(nmax, lsb, amax)) return false;
   series_out(p, L.w, K, s, g);
   for (int k = lane; k < K; k += 64) {
     L.acc[k] = fast_identity<F>();

@@ -76,10 +76,15 @@ def lsb_exp(x: float) -> int:
 
 
 def row_nocert(lsb: int, absmax: float) -> bool:
-    """engine.h row_nocert: the certificate n * absmax <= 2^(52 + lsb) fails already for n = 2."""
+    """engine.h row_nocert: the certificate n * absmax <= 2^(52 + lsb), n * absmax finite, fails
+    already for n = 2.  For 52 + lsb > 1023 the threshold is beyond every double (math.ldexp
+    raises there): only the overflow of 2 * absmax can fail the certificate."""
     if lsb == INT32_MAX or absmax == 0.0:
         return False
-    return math.isinf(absmax) or 2.0 * absmax * (1.0 + 1e-12) > math.ldexp(1.0, 52 + lsb)
+    na = 2.0 * absmax * (1.0 + 1e-12)
+    if not na < math.inf:
+        return True
+    return 52 + lsb <= 1023 and na > math.ldexp(1.0, 52 + lsb)
 
 
 def row_facts(q: bytes, v: bytes) -> RowFacts:
