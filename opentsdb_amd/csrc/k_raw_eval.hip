@@ -741,9 +741,14 @@ __global__ __launch_bounds__(64) void k_raw_top(RawParams p) {
         const int64_t x0 = a.tsf & RAW_TIME_MASK, x1 = b.tsf & RAW_TIME_MASK;
         if (MODE == 1 && !uns && interp == TSDB_INTERP_LERP) {
           // a double LERP strictly inside (x0, x1) stays within [y0, y1] up to a few ulps of
-          // rounding: skipped when even 8 key steps (ulps) above the larger end lie below thr
+          // rounding: skipped when even 8 key steps (ulps) above the larger end lie below thr.  Only
+          // while (x - x0) (y1 - y0) cannot overflow: past that Java's operand is y0 +- Inf (or NaN),
+          // +Inf being the largest key of all (the long branch below asks the same of its product)
           const double y0 = pt_double(a.tsf, a.bits), y1 = pt_double(b.tsf, b.bits);
-          if (isfinite(y0) && isfinite(y1) && f2key(fmax(y0, y1)) + 8 < thr) { skip_all(false, true); continue; }
+          if (isfinite(y0) && isfinite(y1) && isfinite((double)(x1 - x0) * (y1 - y0)) && f2key(fmax(y0, y1)) + 8 < thr) {
+            skip_all(false, true);
+            continue;
+          }
         }
         if (MODE == 0 && !uns && interp == TSDB_INTERP_LERP && x1 > x0) {
           // a long LERP strictly inside the window whose product (x - x0) dy cannot wrap:

@@ -827,8 +827,10 @@ __device__ __forceinline__ FS fs_op(const FS& a, const FS& b) {
 }
 template <int F>
 __device__ __forceinline__ double fs_final(const FS& s) {
-  if (F == F_SUM || F == F_SQUARESUM) return s.n == 0 ? (double)NAN : s.v;
-  if (F == F_AVG) return s.n == 0 ? (double)NAN : s.v / (double)s.n;
+  // Sum / Avg start from 0. (Aggregators.java :247, :383): a bucket of nothing but -0.0 adds to +0.0,
+  // while a run of the segmented reduction starts from its first value
+  if (F == F_SUM || F == F_SQUARESUM) return s.n == 0 ? (double)NAN : 0.0 + s.v;
+  if (F == F_AVG) return s.n == 0 ? (double)NAN : (0.0 + s.v) / (double)s.n;
   if (F == F_COUNT) return (double)s.n;
   if (F == F_MIN) return s.v == INFINITY ? (double)NAN : s.v;
   if (F == F_MAX) return s.v == -INFINITY ? (double)NAN : s.v;
@@ -2910,8 +2912,16 @@ __device__ __forceinline__ PState ps_merge(int ga, PState A, const PState& B) {
       {
         const double na = A.n, nb = B.n, n = na + nb;
         const double delta = B.a - A.a;
-        A.a = A.a + delta * nb / n;
-        A.b = A.b + B.b + delta * delta * na * nb / n;
+        const double nm = A.a + delta * nb / n;
+        double b = A.b + B.b + delta * delta * na * nb / n;
+        // a mean that is infinite or NaN: the sequential recurrence (StdDev.runDouble :553-561) has met
+        // x - old_mean = +-Inf, after which its M2 is -Inf or NaN and the result NaN, never +Inf
+        if (!isfinite(delta)) b = (double)NAN;
+        // one value joins: the recurrence's own step (:556-558; nm is its new mean, delta * 1 / n), so
+        // a fold of single-value states in series order keeps Java's bits
+        if (B.n == 1) b = A.b + delta * (B.a - nm);
+        A.a = nm;
+        A.b = b;
         A.n = A.n + B.n;
       }
       break;

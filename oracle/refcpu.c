@@ -184,10 +184,6 @@ static double pct_value(int a) {
 /* 0 = LEGACY (estimation null), 3 = R_3, 7 = R_7 */
 static int pct_est(int a) { int b = (a - TSDB_AGG_P999) / 6; return b == 0 ? 0 : (b == 1 ? 3 : 7); }
 
-static int cmp_double(const void* a, const void* b) {
-  double x = *(const double*)a, y = *(const double*)b;
-  return x < y ? -1 : (x > y ? 1 : 0);
-}
 /* Double.compareTo (Collections.sort of a List<Double>): -0.0 before 0.0 (NaNs are dropped) */
 static int cmp_double_total(const void* a, const void* b) {
   double x = *(const double*)a, y = *(const double*)b;
@@ -202,7 +198,11 @@ static int cmp_double_total(const void* a, const void* b) {
 static double percentile_eval(double* work, int64_t n, double quantile, int est) {
   if (n == 0) return NAN;
   if (n == 1) return work[0];
-  qsort(work, (size_t)n, sizeof(double), cmp_double);
+  /* KthSelector.select ends in Arrays.sort of the range that holds k (the whole array when n <= 15,
+   * MIN_SELECT_SIZE): a total order with -0.0 before 0.0.  Above 15 values its partition steps
+   * compare with < and >, and which of two zeros of different sign lands on rank k is left to
+   * them; the total order is used there too. */
+  qsort(work, (size_t)n, sizeof(double), cmp_double_total);
   const double p = quantile / 100.0;
   double pos;
   if (est == 3) {
