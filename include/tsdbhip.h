@@ -227,6 +227,27 @@ int tsdbhip_init(int device, tsdbhip_ctx** out);
 void tsdbhip_destroy(tsdbhip_ctx* ctx);
 /* Copy a host batch into HBM (re-laid out: rows 16-B aligned).  Replaces any previous batch. */
 int tsdbhip_load(tsdbhip_ctx* ctx, const tsdbhip_batch* host_batch);
+/* New group ids and tag-filter verdicts for the resident series, without a reload (DESIGN.md
+ * 5.11).  group_id[i] is the new group of series i of the loaded batch, in batch order: the
+ * order of the tsdbhip_batch / tsdbhip_cell_batch given to the load, or for tsdbhip_synth the
+ * store's own order, as tsdbhip_batch_download returns it right after the synth.  n_series must
+ * equal the number of series loaded.  Afterwards the context answers every entry point as if the
+ * loaded batch, restricted to the series whose id is not TSDB_GROUP_EXCLUDED (batch order kept),
+ * had been loaded afresh with these ids, bit for bit; only ids that name a series by batch
+ * position (tsdbhip_rollup_download's series, the multi-device NONE numbering) keep naming
+ * positions of the batch as loaded.  Excluded series stay resident: any sequence of calls is
+ * equivalent to the last one applied to the original load.  n_groups becomes max(group_id) + 1;
+ * every series excluded is legal.  Cells of an earlier tsdbhip_rollup_run / tsdbhip_preagg_run
+ * are dropped; a tsdbhip_load_cells compaction error of an excluded series is not raised (the
+ * scan would not have read that row).  No cell byte moves and nothing is re-indexed: the cost is
+ * 48 bytes a row on the device.
+ * TSDB_E_ILLEGAL_ARGUMENT: null pointers, another n_series, an id below -2.
+ * TSDB_E_NOT_IMPLEMENTED: a multi-device context, a rollup batch, a batch loaded by
+ * tsdbhip_load_shard / tsdbhip_synth_shard (per-rank regrouping needs a global group numbering).
+ * An error leaves the previous grouping as it was. */
+#define TSDB_GROUP_NONE     (-1)   /* as tsdbhip_batch.group_id: no matching group-by tag */
+#define TSDB_GROUP_EXCLUDED (-2)   /* the series does not match the query's tag filters */
+int tsdbhip_regroup(tsdbhip_ctx* ctx, const int32_t* group_id, int64_t n_series);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:

@@ -60,6 +60,10 @@ CAL_NONE, CAL_MS, CAL_S, CAL_M, CAL_H, CAL_D, CAL_W, CAL_N, CAL_Y = range(9)
 
 QF_ORDERED = 0x1
 
+# tsdbhip_regroup / tsdbhip_batch.group_id words (tsdbhip.h TSDB_GROUP_*)
+GROUP_NONE = -1       # no matching group-by tag
+GROUP_EXCLUDED = -2   # the series does not match the query's tag filters
+
 LONG_MAX = (1 << 63) - 1
 
 

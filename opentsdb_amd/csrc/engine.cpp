@@ -395,6 +395,18 @@ struct tsdbhip_ctx {
   DevBuf rows, srp, qual, val, gid;
   DevBuf val2;                         // int16 copy of vle-integer values (k_index), at qualifier offsets
   DevBuf hint, ilist, icnt;            // k_index scratch: row classes, rows by class, class counts
+  // tsdbhip_regroup: every loaded series stays resident; those a regroup excluded sit after the
+  // visible ones -- positions [n_series, n_series_loaded) of rows / srp / gid and of the host
+  // mirrors below, rows [n_rows, n_rows_loaded) -- where no query looks
+  int64_t n_series_loaded = 0, n_rows_loaded = 0;
+  bool regroup_ok = false;             // loaded by tsdbhip_load / _load_cells / _synth (not a shard, not a rollup batch)
+  DevBuf rows2, srp2, gid2;            // the gather's destination, swapped with rows / srp / gid
+  DevBuf rg_ent;                       // [n_series_loaded] RegroupParams.ent
+  HostBuf rg_stage;                    // ... page-locked
+  HostBuf rg_rows;                     // the gathered descriptors, downloaded for the host mirrors
+  void* rg_tmp = nullptr;              // the scan's temporary storage
+  size_t rg_tmp_bytes = 0;
+  std::vector<uint8_t> h_excl;         // [batch index] excluded by the last regroup (empty: none)
   std::vector<int64_t> h_srp;          // [n_series+1]
   std::vector<uint32_t> h_base;        // [n_rows]
   std::vector<uint32_t> h_ndp;         // [n_rows]
@@ -801,8 +813,11 @@ extern "C" int tsdbhip_init(int device, tsdbhip_ctx** out) {
 
 static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
-                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp})
+                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent})
     b->release();
+  c->n_series_loaded = c->n_rows_loaded = 0;
+  c->regroup_ok = false;
+  c->h_excl.clear();
   c->none_tiles_ready = false;
   c->acct_valid = false;
   c->seqd_valid = false;
@@ -878,6 +893,9 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   if (c->pg.tmp) (void)hipFree(c->pg.tmp);
   for (auto& e : c->pg.ev) if (e) (void)hipEventDestroy(e);
   if (c->cmp_tmp) (void)hipFree(c->cmp_tmp);
+  if (c->rg_tmp) (void)hipFree(c->rg_tmp);
+  c->rg_stage.release();
+  c->rg_rows.release();
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
   for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
@@ -1007,6 +1025,48 @@ static int build_none_tiles(tsdbhip_ctx* c) {
   return 0;
 }
 
+// The part of a load that depends on which series are visible and how they are grouped: the
+// dominant row classes of the k_fast / k_pct_rows specialisations over the visible rows' host
+// mirrors, then the tiles.  finish_load ends with it, and so does tsdbhip_regroup.
+static int finish_classes(tsdbhip_ctx* c) {
+  int64_t cls[2][2] = {{0, 0}, {0, 0}};   // [qw 2/4][vl 4/8] uniform float rows
+  int64_t cls_vle = 0;                    // 2-byte qualifiers, 1-2 byte integers, one chunk
+  int64_t cls_pct[2][9] = {};             // [qw 2/4][vl]: uniform sorted rows of <= 512 dp
+  int64_t cls_vonly[2] = {};              // [qw 2/4]: those of 4-byte values, all-float without NaN or all-int
+  uint32_t vonly_max[2] = {};             // [qw 2/4]: their longest row
+  for (int64_t r = 0; r < c->n_rows; r++) {
+    const uint32_t f = c->h_flags[r], ndp = c->h_ndp[r];
+    const uint32_t qw = f & ROW_QW_MASK, vl = (f & ROW_VL_MASK) >> ROW_VL_SHIFT;
+    if ((f & ROW_ALLF) && !(f & (ROW_ERR | ROW_NAN | ROW_UNSORTED)) && (qw == 2 || qw == 4) && (vl == 4 || vl == 8))
+      cls[qw == 4][vl == 8] += ndp;
+    if ((f & ROW_ALLI) && (f & ROW_VLE2) && !(f & (ROW_ERR | ROW_UNSORTED)) && qw == 2 && ndp <= 512)
+      cls_vle += ndp;
+    if (!(f & (ROW_ERR | ROW_UNSORTED)) && (qw == 2 || qw == 4) && (vl == 1 || vl == 2 || vl == 4 || vl == 8) &&
+        ndp <= 512)
+      cls_pct[qw == 4][vl] += ndp;
+    if (!(f & (ROW_ERR | ROW_UNSORTED)) && (qw == 2 || qw == 4) && vl == 4 && ndp <= 512 &&
+        (((f & ROW_ALLF) && !(f & ROW_NAN)) || (f & ROW_ALLI))) {
+      cls_vonly[qw == 4] += ndp;
+      vonly_max[qw == 4] = std::max(vonly_max[qw == 4], ndp);
+    }
+  }
+  // the two largest k_fast row classes by datapoints
+  struct Cand { int64_t n; int qw, vl; };
+  std::vector<Cand> cand = {{cls[0][0], 2, 4}, {cls[0][1], 2, 8}, {cls[1][0], 4, 4}, {cls[1][1], 4, 8}, {cls_vle, 2, 0}};
+  std::stable_sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return x.n > y.n; });
+  c->fast_qw = c->fast_vl = c->fast_qw2 = c->fast_vl2 = 0;
+  if (cand[0].n > 0) { c->fast_qw = cand[0].qw; c->fast_vl = cand[0].vl; }
+  if (cand[1].n > 0) { c->fast_qw2 = cand[1].qw; c->fast_vl2 = cand[1].vl; }
+  c->pct_qw = c->pct_vl = 0;
+  int64_t best = 0;
+  for (int a = 0; a < 2; a++)
+    for (int v = 1; v <= 8; v++)
+      if (cls_pct[a][v] > best) { best = cls_pct[a][v]; c->pct_qw = a ? 4 : 2; c->pct_vl = v; }
+  c->pct_vonly = c->pct_vl == 4 && best > 0 && cls_vonly[c->pct_qw == 4] == best;
+  c->pct_v6 = c->pct_vonly && vonly_max[c->pct_qw == 4] <= 384;
+  return build_tiles(c);
+}
+
 static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   // classify rows on the device, then fetch ndp for host-side accounting
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
@@ -1084,48 +1144,17 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   c->h_qlen.resize(c->n_rows);
   c->h_vlen.resize(c->n_rows);
   c->h_flags.resize(c->n_rows);
-  int64_t cls[2][2] = {{0, 0}, {0, 0}};   // [qw 2/4][vl 4/8] uniform float rows
-  int64_t cls_vle = 0;                    // 2-byte qualifiers, 1-2 byte integers, one chunk
-  int64_t cls_pct[2][9] = {};             // [qw 2/4][vl]: uniform sorted rows of <= 512 dp
-  int64_t cls_vonly[2] = {};              // [qw 2/4]: those of 4-byte values, all-float without NaN or all-int
-  uint32_t vonly_max[2] = {};             // [qw 2/4]: their longest row
   for (int64_t r = 0; r < c->n_rows; r++) {
     c->h_ndp[r] = back[r].ndp;
     c->h_base[r] = back[r].base;
     c->h_qlen[r] = back[r].qlen;
     c->h_vlen[r] = back[r].vlen;
     c->h_flags[r] = back[r].flags;
-    const uint32_t f = back[r].flags;
-    const uint32_t qw = f & ROW_QW_MASK, vl = (f & ROW_VL_MASK) >> ROW_VL_SHIFT;
-    if ((f & ROW_ALLF) && !(f & (ROW_ERR | ROW_NAN | ROW_UNSORTED)) && (qw == 2 || qw == 4) && (vl == 4 || vl == 8))
-      cls[qw == 4][vl == 8] += back[r].ndp;
-    if ((f & ROW_ALLI) && (f & ROW_VLE2) && !(f & (ROW_ERR | ROW_UNSORTED)) && qw == 2 && back[r].ndp <= 512)
-      cls_vle += back[r].ndp;
-    if (!(f & (ROW_ERR | ROW_UNSORTED)) && (qw == 2 || qw == 4) && (vl == 1 || vl == 2 || vl == 4 || vl == 8) &&
-        back[r].ndp <= 512)
-      cls_pct[qw == 4][vl] += back[r].ndp;
-    if (!(f & (ROW_ERR | ROW_UNSORTED)) && (qw == 2 || qw == 4) && vl == 4 && back[r].ndp <= 512 &&
-        (((f & ROW_ALLF) && !(f & ROW_NAN)) || (f & ROW_ALLI))) {
-      cls_vonly[qw == 4] += back[r].ndp;
-      vonly_max[qw == 4] = std::max(vonly_max[qw == 4], back[r].ndp);
-    }
   }
-  // the two largest k_fast row classes by datapoints
-  struct Cand { int64_t n; int qw, vl; };
-  std::vector<Cand> cand = {{cls[0][0], 2, 4}, {cls[0][1], 2, 8}, {cls[1][0], 4, 4}, {cls[1][1], 4, 8}, {cls_vle, 2, 0}};
-  std::stable_sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return x.n > y.n; });
-  c->fast_qw = c->fast_vl = c->fast_qw2 = c->fast_vl2 = 0;
-  if (cand[0].n > 0) { c->fast_qw = cand[0].qw; c->fast_vl = cand[0].vl; }
-  if (cand[1].n > 0) { c->fast_qw2 = cand[1].qw; c->fast_vl2 = cand[1].vl; }
-  c->pct_qw = c->pct_vl = 0;
-  int64_t best = 0;
-  for (int a = 0; a < 2; a++)
-    for (int v = 1; v <= 8; v++)
-      if (cls_pct[a][v] > best) { best = cls_pct[a][v]; c->pct_qw = a ? 4 : 2; c->pct_vl = v; }
-  c->pct_vonly = c->pct_vl == 4 && best > 0 && cls_vonly[c->pct_qw == 4] == best;
-  c->pct_v6 = c->pct_vonly && vonly_max[c->pct_qw == 4] <= 384;
+  c->n_series_loaded = c->n_series;
+  c->n_rows_loaded = c->n_rows;
   // malformed rows are reported lazily, when a query reads them (as the reference does)
-  return build_tiles(c);
+  return finish_classes(c);
 }
 
 // RowSeq.addRow (src/core/RowSeq.java:91-222): ordered merge of the remote cell into the
@@ -1280,7 +1309,9 @@ static int load_body(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<i
   HIP_OK(h2d(c, c->val.p, hv.data(), hv.size(), c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
   if (c->n_series) HIP_OK(hipMemcpy(c->gid.p, c->h_group.data(), c->n_series * 4, hipMemcpyHostToDevice));
-  return finish_load(c, rd);
+  const int rc = finish_load(c, rd);
+  c->regroup_ok = rc == 0 && !cand;   // (a shard's group numbering is global: tsdbhip_regroup refuses it)
+  return rc;
 }
 
 static int load_impl(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<int64_t>* cand = nullptr) {
@@ -2253,6 +2284,7 @@ extern "C" int tsdbhip_load_cells(tsdbhip_ctx* c, const tsdbhip_cell_batch* cb) 
   mark("finish_load");
   c->cmp_errs = std::move(errs);
   c->compact_ms = cmp_ms;
+  c->regroup_ok = rc == 0;
   return rc;
 }
 
@@ -2343,7 +2375,7 @@ extern "C" int tsdbhip_load_shard(tsdbhip_ctx* c, const tsdbhip_batch* b, int mo
 
 // Batch positions [p0, p1) of the synthetic store (series sorted by group; group g holds
 // global series g, g + G, g + 2G, ...): one GPU's contiguous shard of the whole store.
-static int synth_impl(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t p0, int64_t p1) {
+static int synth_impl(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t p0, int64_t p1, bool shard) {
   if (!c || !sp) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
   CtxLock lk(c);
   HIP_OK(hipSetDevice(c->device));
@@ -2451,17 +2483,148 @@ static int synth_impl(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t p0, 
     for (int64_t i = std::max(grp_off[g], p0); i < std::min(grp_off[g + 1], p1); i++) c->h_group[i - p0] = (int32_t)g;
   std::iota(c->h_orig.begin(), c->h_orig.end(), 0);
   HIP_OK(hipStreamSynchronize(c->stream));
-  return finish_load(c, rd);
+  const int rc = finish_load(c, rd);
+  c->regroup_ok = rc == 0 && !shard;
+  return rc;
 }
 
 extern "C" int tsdbhip_synth(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp) {
   if (c && c->md) return tsdb::md_synth(c, sp);
-  return synth_impl(c, sp, 0, sp ? sp->n_series : 0);
+  return synth_impl(c, sp, 0, sp ? sp->n_series : 0, false);
 }
 
 extern "C" int tsdbhip_synth_shard(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t pos_begin, int64_t pos_end) {
   MD_REFUSE(c, "tsdbhip_synth_shard");
-  return synth_impl(c, sp, pos_begin, pos_end);
+  return synth_impl(c, sp, pos_begin, pos_end, true);
+}
+
+// New group ids and tag-filter verdicts for the resident series: the series'
+// descriptors are gathered into the order a fresh load of the visible series with these ids
+// would have given them -- group ascending, then the ungrouped, batch order inside each -- with
+// the excluded series behind; no cell byte moves and nothing is re-indexed.  group_id is in
+// batch order, the index space of h_orig.
+extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t n_series) {
+  if (!c || !group_id) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_regroup");
+  CtxLock lk(c);
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_regroup over a rollup batch (tsdbhip_load_rollup)");
+  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
+  if (!c->regroup_ok && (N > 0 || n_series != 0))
+    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_regroup needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                        "tsdbhip_synth (a shard's groups are numbered globally)");
+  if (n_series != N)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_series is " + std::to_string(n_series) + ", the loaded batch has " +
+                                             std::to_string(N) + " series");
+  int32_t maxg = -1;
+  for (int64_t s = 0; s < N; s++) {
+    if (group_id[s] < TSDB_GROUP_EXCLUDED) return fail(TSDB_E_ILLEGAL_ARGUMENT, "group id below TSDB_GROUP_EXCLUDED");
+    maxg = std::max(maxg, group_id[s]);
+  }
+  if (N == 0) return 0;
+  HIP_OK(hipSetDevice(c->device));
+  const int64_t G = (int64_t)maxg + 1;
+  // the new order: current resident positions, stably sorted by (key, batch index).  Keys are
+  // the group, G for an ungrouped series, G + 1 for an excluded one; the sort is a counting sort
+  // over the positions taken in batch order (pos: batch index -> current position).
+  std::vector<int32_t> pos(N);
+  for (int64_t i = 0; i < N; i++) pos[c->h_orig[i]] = (int32_t)i;
+  auto key = [&](int64_t b) -> int64_t {
+    const int32_t g = group_id[b];
+    return g == TSDB_GROUP_EXCLUDED ? G + 1 : g < 0 ? G : g;
+  };
+  std::vector<int64_t> start(G + 3, 0);
+  for (int64_t b = 0; b < N; b++) start[key(b) + 1]++;
+  for (int64_t k = 0; k < G + 2; k++) start[k + 1] += start[k];
+  const int64_t n_vis = start[G + 1];
+  HIP_OK(c->rg_stage.ensure((size_t)N * sizeof(int2)));
+  int2* ent = reinterpret_cast<int2*>(c->rg_stage.p);
+  std::vector<int64_t> n_orig(N);
+  std::vector<int32_t> n_group(N);
+  {
+    std::vector<int64_t> cur(start.begin(), start.end() - 1);
+    for (int64_t b = 0; b < N; b++) {
+      const int64_t k = key(b), i = cur[k]++;
+      ent[i].x = pos[b];
+      ent[i].y = (int32_t)k;
+      n_orig[i] = b;
+      n_group[i] = (int32_t)k;
+    }
+  }
+  // device: the new series_row_ptr, descriptors and gid into the second buffers
+  HIP_OK(c->rg_ent.ensure((size_t)N * sizeof(int2)));
+  HIP_OK(c->rows2.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RowDesc)));
+  HIP_OK(c->srp2.ensure((size_t)(N + 1) * 8));
+  HIP_OK(c->gid2.ensure((size_t)N * 4));
+  HIP_OK(hipMemcpyAsync(c->rg_ent.p, ent, (size_t)N * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+  RegroupParams rp{};
+  rp.ent = c->rg_ent.as<int2>();
+  rp.srp_old = c->srp.as<int64_t>();
+  rp.rows_old = c->rows.as<RowDesc>();
+  rp.n_series = N;
+  rp.n_rows = NR;
+  rp.srp_new = c->srp2.as<int64_t>();
+  rp.rows_new = c->rows2.as<RowDesc>();
+  rp.gid_new = c->gid2.as<int32_t>();
+  HIP_OK(regroup_scan(rp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(launch_regroup(rp, c->stream));
+  // host mirrors in the new order: series_row_ptr from the old one while the device works, the
+  // per-row mirrors from a download of the gathered descriptors -- a sequential pass over 48 B a
+  // row, where permuting the five old mirrors is five cache misses a row (17 ms against 34 ms
+  // for a million scattered one-row series, profiles/regroup/regroup_dl_*.log)
+  HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RowDesc)));
+  if (NR)
+    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  std::vector<int64_t> n_srp(N + 1, 0);
+  for (int64_t i = 0; i < N; i++) n_srp[i + 1] = n_srp[i] + (c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x]);
+  std::vector<uint32_t> n_base(NR), n_ndp(NR), n_qlen(NR), n_vlen(NR), n_flags(NR);
+  HIP_OK(hipStreamSynchronize(c->stream));
+  {
+    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
+    for (int64_t r = 0; r < NR; r++) {
+      n_base[r] = back[r].base;
+      n_ndp[r] = back[r].ndp;
+      n_qlen[r] = back[r].qlen;
+      n_vlen[r] = back[r].vlen;
+      n_flags[r] = back[r].flags;
+    }
+  }
+  // commit: from here on the context holds the new grouping
+  std::swap(c->rows, c->rows2);
+  std::swap(c->srp, c->srp2);
+  std::swap(c->gid, c->gid2);
+  c->h_srp.swap(n_srp);
+  c->h_base.swap(n_base);
+  c->h_ndp.swap(n_ndp);
+  c->h_qlen.swap(n_qlen);
+  c->h_vlen.swap(n_vlen);
+  c->h_flags.swap(n_flags);
+  c->h_orig.swap(n_orig);
+  c->h_group.swap(n_group);
+  c->n_series = n_vis;
+  c->n_rows = c->h_srp[n_vis];
+  c->n_groups = G;
+  c->max_series_rows = 0;
+  for (int64_t i = 0; i < n_vis; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
+  if (n_vis == N) {
+    c->h_excl.clear();
+  } else {
+    c->h_excl.assign(N, 0);
+    for (int64_t i = n_vis; i < N; i++) c->h_excl[c->h_orig[i]] = 1;
+  }
+  // what a load invalidates of the state that depends on the series' order or groups
+  c->none_tiles_ready = false;
+  c->acct_valid = false;
+  c->seqd_valid = false;
+  c->row_ser_valid = false;
+  c->n_grouped = -1;
+  c->mdp_valid = false;
+  c->ro_meta_valid = false;
+  c->lc_valid = false;
+  c->calc_valid = false;
+  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the grouping they came from)
+  c->pg.cells = 0;
+  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  return finish_classes(c);
 }
 
 extern "C" int tsdbhip_batch_sizes(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_rows, uint64_t* qual_bytes,
@@ -2857,7 +3020,7 @@ int scan_bounds_of(tsdbhip_ctx* c, const tsdbhip_query* q, int64_t& ss, int64_t&
 // (SaltScanner.processRow :825-830 closes the scanner with the exception), in scan order.
 int cmp_scan_check(tsdbhip_ctx* c, const Plan& P) {
   for (const auto& e : c->cmp_errs)
-    if (e.base >= P.ss && e.base < P.se)
+    if (e.base >= P.ss && e.base < P.se && !(e.series < (int64_t)c->h_excl.size() && c->h_excl[e.series]))
       return fail(e.code, e.code == TSDB_E_NOT_IMPLEMENTED
                               ? "query-time compaction of a row this engine does not restate (a compacted cell out of "
                                 "time order, or a datapoint column without a value)"

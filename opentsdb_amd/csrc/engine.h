@@ -503,6 +503,20 @@ struct PreaggParams {
 hipError_t launch_preagg_size(const PreaggParams& p, hipStream_t s);
 hipError_t preagg_scan(const uint8_t* code, uint64_t* off, int64_t n1, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_preagg_write(const PreaggParams& p, hipStream_t s);
+
+// tsdbhip_regroup (k_regroup.hip): the loaded series in a new order.  Entry i of `ent` is the
+// series at new position i: x = its current resident position, y = its new group word.
+struct RegroupParams {
+  const int2* ent;            // [n_series]
+  const int64_t* srp_old;     // [n_series + 1] current series_row_ptr (every loaded series)
+  const RowDesc* rows_old;    // [n_rows]
+  int64_t n_series, n_rows;   // loaded counts (the excluded tail included)
+  int64_t* srp_new;           // [n_series + 1]
+  RowDesc* rows_new;          // [n_rows]
+  int32_t* gid_new;           // [n_series]
+};
+hipError_t regroup_scan(const RegroupParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_regroup(const RegroupParams& p, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

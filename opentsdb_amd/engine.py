@@ -35,6 +35,7 @@ EXPORTS = [
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
+    "tsdbhip_regroup",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -116,6 +117,7 @@ def lib():
         L.tsdbhip_host_free.argtypes = [vp]
         L.tsdbhip_host_free.restype = None
         L.tsdbhip_load.argtypes = [vp, C.POINTER(abi.Batch)]
+        L.tsdbhip_regroup.argtypes = [vp, C.c_void_p, C.c_int64]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
         L.tsdbhip_batch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]
@@ -367,6 +369,15 @@ class Engine:
     def load(self, batch: abi.HostBatch):
         _check(lib().tsdbhip_load(self.ctx, C.byref(batch.c)))
         self._batch = batch
+
+    def regroup(self, group_ids):
+        """tsdbhip_regroup: new group ids for the loaded series, in the order of the batch given to
+        the load (abi.GROUP_NONE: no group-by tag, abi.GROUP_EXCLUDED: filtered out).  The cells
+        stay where they are; the next queries see the restricted, regrouped batch."""
+        ids = np.ascontiguousarray(group_ids, dtype=np.int32)
+        if ids.ndim != 1:
+            raise ValueError("group_ids must be one-dimensional")
+        _check(lib().tsdbhip_regroup(self.ctx, ids.ctypes.data, len(ids)))
 
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""

@@ -559,3 +559,63 @@ class TsdbQuery:
                 cur = nxt
         finally:
             self.downsampler = saved
+
+
+class ResidentSpans:
+    """Every span of one metric over [scan_start_s, scan_end_s), loaded once and kept in HBM;
+    each query then only regroups the resident series (Engine.regroup, tsdbhip_regroup) instead
+    of filtering, flattening and uploading a batch of its own as TsdbQuery.build_batch does.
+
+    run(tsdb_query) answers a raw-table TsdbQuery over `store` whose scan range lies inside the
+    resident one: the query's tag filters decide which resident spans are visible
+    (abi.GROUP_EXCLUDED for the others) and its group-by tags number the visible ones, with the
+    query's own _filters() / _groups() logic."""
+
+    def __init__(self, store: MockStore, metric: str, scan_start_s: int, scan_end_s: int, engine=None):
+        if scan_end_s <= scan_start_s:
+            raise ValueError("empty resident scan range")
+        self.store = store
+        self.metric = metric
+        self.scan_start_s = scan_start_s
+        self.scan_end_s = scan_end_s
+        if engine is None:
+            from .engine import default_engine
+            engine = default_engine()
+        self.engine = engine
+        self.spans = store.scan(metric, scan_start_s, scan_end_s)   # SpanCmp order, no filter
+        self.span_keys = [sk for sk, _ in self.spans]
+        # (loaded ungrouped: every run() regroups before it queries)
+        self.engine.load(make_batch(self.spans, [abi.GROUP_NONE] * len(self.spans)))
+
+    def group_ids(self, query: TsdbQuery):
+        """(group id of every resident span for `query`, group keys in emission order)."""
+        f = query._filters()
+        if f is None:   # an unknown tag name or literal value: no series matches
+            return [abi.GROUP_EXCLUDED] * len(self.spans), []
+        pred, group_bys = f
+        visible = [i for i, sk in enumerate(self.span_keys) if pred(sk[1])]
+        keys, gids = TsdbQuery._groups([self.spans[i] for i in visible], group_bys)
+        ids = [abi.GROUP_EXCLUDED] * len(self.spans)
+        for i, g in zip(visible, gids):
+            ids[i] = g
+        return ids, keys
+
+    def run(self, query: TsdbQuery):
+        """DataPoints[] of the query, keyed as TsdbQuery._run_raw keys them."""
+        if query.store is not self.store or query.metric != self.metric:
+            raise ValueError("the query is over another store or metric than the resident spans")
+        if query.tableToBeScanned()[0] != "raw":
+            raise ValueError("the resident spans answer raw-table queries only")
+        s, e = query.scan_bounds()
+        if s < self.scan_start_s or e > self.scan_end_s:
+            raise ValueError(f"the query scans [{s}, {e}), outside the resident range "
+                             f"[{self.scan_start_s}, {self.scan_end_s})")
+        ids, keys = self.group_ids(query)
+        if not self.spans:
+            return []
+        self.engine.regroup(ids)
+        out = []
+        for gid, ts, bits, isi in self.engine.run(query.to_abi()):
+            key = keys[gid] if (query.aggregator != "none" and 0 <= gid < len(keys)) else ()
+            out.append(DataPoints(gid, ts, bits, isi, query.metric, key))
+        return out
