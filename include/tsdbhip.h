@@ -198,7 +198,8 @@ const char* tsdbhip_last_error(void);
  * allocates the int16 value copy late, as a store with no spare memory does), CMP_CHUNK,
  * CMP_ROWS, CMP_ONEPASS, PCT_ROWS, PCT_KEYS,
  * PCT_VONLY, PCT_V6, SEL_FUSED, SEL_COLS, SEL_WIN, SEL_WAVE, SEL_REG, SELOPS, RAW_LERPW,
- * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT, TRACE, DBG
+ * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT,
+ * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit), TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
  * its production choice, which is every option's initial state.  The library reads no
  * environment variable: an inherited environment cannot change its kernels.  DBG is honoured
@@ -248,6 +249,41 @@ int tsdbhip_load(tsdbhip_ctx* ctx, const tsdbhip_batch* host_batch);
 #define TSDB_GROUP_NONE     (-1)   /* as tsdbhip_batch.group_id: no matching group-by tag */
 #define TSDB_GROUP_EXCLUDED (-2)   /* the series does not match the query's tag filters */
 int tsdbhip_regroup(tsdbhip_ctx* ctx, const int32_t* group_id, int64_t n_series);
+/* Newly scanned rows appended to the resident batch, without a reload.  `delta`
+ * is an ordinary batch: the rows a rescan of [live hour, new scan end) returned, for resident
+ * series and for series not resident so far.  series_index[i] is delta series i's index in the
+ * batch AFTER the append, which has N' = N + #new series; resident series keep their relative
+ * order, so a resident series' old batch index is series_index[i] minus the number of new series
+ * with a smaller index.  series_new[i] != 0 marks a series that is not resident so far.  After
+ * the call "batch order" (tsdbhip_regroup's ids, NONE emission) means the new indices.
+ * An upsert by (series, base time) restricted to what a tail scan yields: a delta row of a
+ * resident series either lies after every resident row of the series (appended) or has the base
+ * time of the series' LAST resident row, which it then REPLACES (the rescanned cell is the row as
+ * the store now holds it; it is not merged).  Rows of the delta that share (series, base) are
+ * merged first, as tsdbhip_load merges them.  The replaced row's bytes stay in the blobs (dead
+ * bytes, counted in `info`, not reclaimed).  A new series takes delta->group_id[i] (>= 0,
+ * TSDB_GROUP_NONE or TSDB_GROUP_EXCLUDED); a resident series keeps its group or its exclusion.
+ * Afterwards the context answers every entry point as a fresh tsdbhip_load of the merged batch,
+ * followed by the tsdbhip_regroup that reproduces the present ids, would, bit for bit --
+ * except that tsdbhip_debug_index and timing.index_ms describe the delta's index pass, cells of
+ * an earlier tsdbhip_rollup_run / tsdbhip_preagg_run are dropped, and a tsdbhip_load_cells
+ * compaction error is renumbered (dropped when its row is replaced).  A malformed delta cell is
+ * reported by the first query that reads it, as at load.  The blobs grow by the developer option
+ * APPEND_RESERVE per cent beyond the need when they have to be re-allocated.
+ * TSDB_E_ILLEGAL_ARGUMENT: null pointers, an index outside [0, N'), repeated indices, an implied
+ * old index outside [0, N), a new series' id below -2, the delta's own batch invariants failing.
+ * TSDB_E_NOT_IMPLEMENTED: a multi-device context, a rollup batch, a shard load; a delta row
+ * earlier than its series' last resident row (back-fill, or replacing a row that is not the
+ * last): reload instead.  TSDB_E_NOMEM: the grown blobs do not fit beside the old ones.
+ * An error leaves the resident batch as it was.  A delta without series is a no-op. */
+typedef struct {
+  int64_t series_added, rows_added, rows_replaced;
+  uint64_t qual_capacity, val_capacity;   /* bytes the blobs now have allocated */
+  uint64_t qual_dead, val_dead;           /* bytes of replaced rows still in the blobs, since the load */
+  int32_t grew;                           /* this call re-allocated the blobs */
+} tsdbhip_append_info;
+int tsdbhip_append(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* series_index,
+                   const uint8_t* series_new, tsdbhip_append_info* info /* may be NULL */);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:

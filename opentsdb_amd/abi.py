@@ -214,6 +214,20 @@ class PreaggSpec(C.Structure):
     ]
 
 
+class AppendInfo(C.Structure):
+    """tsdbhip_append_info: what a tsdbhip_append did to the resident batch."""
+    _fields_ = [
+        ("series_added", C.c_int64),
+        ("rows_added", C.c_int64),
+        ("rows_replaced", C.c_int64),
+        ("qual_capacity", C.c_uint64),
+        ("val_capacity", C.c_uint64),
+        ("qual_dead", C.c_uint64),
+        ("val_dead", C.c_uint64),
+        ("grew", C.c_int32),
+    ]
+
+
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,
               ds_all: bool = False, rate: bool = False, counter: bool = False,

@@ -14,7 +14,9 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <numeric>
 #include <string>
@@ -407,6 +409,11 @@ struct tsdbhip_ctx {
   void* rg_tmp = nullptr;              // the scan's temporary storage
   size_t rg_tmp_bytes = 0;
   std::vector<uint8_t> h_excl;         // [batch index] excluded by the last regroup (empty: none)
+  // tsdbhip_append: the blobs are capacity-managed (qual.n / val.n >= qual_bytes / val_bytes +
+  // BLOB_SLACK, val2.n == qual.n when present); bytes of replaced rows stay where they are
+  uint64_t qual_dead = 0, val_dead = 0;
+  DevBuf ap_rows, ap_ent, ap_touch;    // the delta's descriptors, AppendParams.ent, the touched series
+  HostBuf ap_stage;                    // ... page-locked (entries, then the touched list)
   std::vector<int64_t> h_srp;          // [n_series+1]
   std::vector<uint32_t> h_base;        // [n_rows]
   std::vector<uint32_t> h_ndp;         // [n_rows]
@@ -638,7 +645,7 @@ const char* const kOptNames[OPT_COUNT] = {
     "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-    "HIST_WS", "HIST_LAYOUT", "TRACE", "DBG"};
+    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "TRACE", "DBG"};
 int opt_index(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < OPT_COUNT; i++)
@@ -666,6 +673,10 @@ extern "C" int tsdbhip_get_option(const char* name, int64_t* value) {
 
 namespace tsdb {
 hipError_t h2d(tsdbhip_ctx* c, void* dst, const void* src, size_t n, hipStream_t st);   // (defined at the end)
+// rows row[0 .. n) of `b` packed where their descriptors say, relative to (q0, v0), the padding up
+// to the next 16 bytes zeroed; on the assembly threads when the rows are large (defined at the end)
+void pack_cells(uint8_t* dq, uint8_t* dv, const tsdbhip_batch* b, const int64_t* row, const RowDesc* rd, int64_t n,
+                uint64_t q0, uint64_t v0);
 }  // namespace tsdb
 
 extern "C" int tsdbhip_host_alloc(uint64_t bytes, void** out) {
@@ -813,8 +824,9 @@ extern "C" int tsdbhip_init(int device, tsdbhip_ctx** out) {
 
 static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
-                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent})
+                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch})
     b->release();
+  c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
   c->regroup_ok = false;
   c->h_excl.clear();
@@ -896,6 +908,7 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   if (c->rg_tmp) (void)hipFree(c->rg_tmp);
   c->rg_stage.release();
   c->rg_rows.release();
+  c->ap_stage.release();
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
   for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
@@ -1327,8 +1340,18 @@ static int load_impl(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<i
 // Span.addRow (src/core/Span.java:177-220): several cells of one series with the same base
 // time (salt-bucket duplicates) merge into one RowSeq (RowSeq.addRow).  Batches without such
 // rows are loaded as given; otherwise the merged batch is built first.
-static int load_with(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<int64_t>* cand) {
-  if (!c || !b) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+struct MergedBatch {
+  std::vector<int64_t> srp;
+  std::vector<uint32_t> base;
+  std::vector<uint64_t> qoff, voff;
+  std::vector<uint8_t> qual, val;
+  tsdbhip_batch m;
+};
+
+// false: no series of `b` has two rows of one base time (or `b` is not well-formed enough to
+// tell: the load's own checks refuse it); true: `out.m` is the batch with such rows merged, its
+// arrays owned by `out`.  Series indices are unchanged by the merge.
+static bool merge_same_base(const tsdbhip_batch* b, MergedBatch& out) {
   bool dup = false;
   if (b->n_series > 0 && b->n_rows > 0 && b->series_row_ptr && b->row_base_time && b->row_qual_off &&
       b->row_val_off && b->qual && b->val) {
@@ -1341,11 +1364,17 @@ static int load_with(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<i
       dup = std::adjacent_find(bases.begin(), bases.end()) != bases.end();
     }
   }
-  if (!dup) return load_impl(c, b, cand);
-  std::vector<int64_t> srp(b->n_series + 1, 0);
-  std::vector<uint32_t> base;
-  std::vector<uint64_t> qoff{0}, voff{0};
-  std::vector<uint8_t> qual, val;
+  if (!dup) return false;
+  std::vector<int64_t>& srp = out.srp;
+  std::vector<uint32_t>& base = out.base;
+  std::vector<uint64_t>&qoff = out.qoff, &voff = out.voff;
+  std::vector<uint8_t>&qual = out.qual, &val = out.val;
+  srp.assign(b->n_series + 1, 0);
+  base.clear();
+  qoff.assign(1, 0);
+  voff.assign(1, 0);
+  qual.clear();
+  val.clear();
   for (int64_t s = 0; s < b->n_series; s++) {
     std::vector<uint32_t> obase;
     std::vector<std::vector<uint8_t>> oq, ov;
@@ -1374,15 +1403,22 @@ static int load_with(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<i
   }
   if (qual.empty()) qual.push_back(0);
   if (val.empty()) val.push_back(0);
-  tsdbhip_batch m = *b;
-  m.n_rows = (int64_t)base.size();
-  m.series_row_ptr = srp.data();
-  m.row_base_time = base.data();
-  m.row_qual_off = qoff.data();
-  m.row_val_off = voff.data();
-  m.qual = qual.data();
-  m.val = val.data();
-  return load_impl(c, &m, cand);   // series indices are unchanged by the merge
+  out.m = *b;
+  out.m.n_rows = (int64_t)base.size();
+  out.m.series_row_ptr = srp.data();
+  out.m.row_base_time = base.data();
+  out.m.row_qual_off = qoff.data();
+  out.m.row_val_off = voff.data();
+  out.m.qual = qual.data();
+  out.m.val = val.data();
+  return true;
+}
+
+static int load_with(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<int64_t>* cand) {
+  if (!c || !b) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MergedBatch mb;
+  if (!merge_same_base(b, mb)) return load_impl(c, b, cand);
+  return load_impl(c, &mb.m, cand);   // series indices are unchanged by the merge
 }
 
 extern "C" int tsdbhip_load(tsdbhip_ctx* c, const tsdbhip_batch* b) {
@@ -2625,6 +2661,426 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   c->pg.cells = 0;
   c->pg.qual_bytes = c->pg.value_bytes = 0;
   return finish_classes(c);
+}
+
+// Newly scanned rows appended to the resident batch.  The delta's cells go to
+// the blobs' tail and are indexed in a descriptor array of their own; k_append then gathers the
+// kept resident descriptors and the delta's into the series order a fresh load of the merged
+// batch, regrouped to the present ids, would have.  Everything is validated and allocated before
+// the resident batch changes; the commit is the swap at the end, as in tsdbhip_regroup.
+extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index,
+                              const uint8_t* series_new, tsdbhip_append_info* info) {
+  if (!c || !delta) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_append");
+  CtxLock lk(c);
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_append over a rollup batch (tsdbhip_load_rollup)");
+  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
+  if (!c->regroup_ok)
+    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_append needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                        "tsdbhip_synth (a shard's groups are numbered globally)");
+  // the delta's own batch invariants (load_body's checks)
+  const tsdbhip_batch* b = delta;
+  if (b->n_series < 0 || b->n_rows < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
+  if (b->n_series > 0 && (!b->series_row_ptr || !b->group_id || !series_index || !series_new))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
+  if (b->n_rows > 0 && (!b->row_base_time || !b->row_qual_off || !b->row_val_off || !b->qual || !b->val))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
+  if (b->n_series > 0 && (b->series_row_ptr[0] != 0 || b->series_row_ptr[b->n_series] != b->n_rows))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr does not cover the rows");
+  for (int64_t s = 0; s < b->n_series; s++)
+    if (b->series_row_ptr[s + 1] < b->series_row_ptr[s]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr not monotonic");
+  for (int64_t r = 0; r < b->n_rows; r++) {
+    if (b->row_qual_off[r + 1] < b->row_qual_off[r] || b->row_val_off[r + 1] < b->row_val_off[r])
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row offsets not monotonic");
+    if (b->row_qual_off[r + 1] - b->row_qual_off[r] > 0xFFFFFFFFull || b->row_val_off[r + 1] - b->row_val_off[r] > 0xFFFFFFFFull)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
+  }
+  auto fill_info = [&](int64_t sa, int64_t ra, int64_t rr, bool grew) {
+    if (!info) return;
+    info->series_added = sa;
+    info->rows_added = ra;
+    info->rows_replaced = rr;
+    info->qual_capacity = c->qual.n;
+    info->val_capacity = c->val.n;
+    info->qual_dead = c->qual_dead;
+    info->val_dead = c->val_dead;
+    info->grew = grew ? 1 : 0;
+  };
+  const int64_t D = b->n_series;
+  if (D == 0) { fill_info(0, 0, 0, false); return 0; }
+  // rows of the delta that share (series, base) merge first, as at load
+  MergedBatch mb;
+  if (merge_same_base(b, mb)) b = &mb.m;
+  if (b->n_rows > INT32_MAX) return fail(TSDB_E_ILLEGAL_ARGUMENT, "the delta has more than 2^31 - 1 rows");
+  const int64_t DR = b->n_rows;
+  // the index spaces: N' = N + #new; delta_of: new batch index -> delta series
+  int64_t K = 0;
+  for (int64_t i = 0; i < D; i++) K += series_new[i] ? 1 : 0;
+  const int64_t N2 = N + K;
+  if (N2 > INT32_MAX) return fail(TSDB_E_ILLEGAL_ARGUMENT, "more than 2^31 - 1 series");
+  std::vector<int32_t> delta_of(N2, -1);
+  std::vector<uint8_t> is_new(N2, 0);
+  for (int64_t i = 0; i < D; i++) {
+    const int64_t x = series_index[i];
+    if (x < 0 || x >= N2)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_index " + std::to_string(x) + " outside [0, " + std::to_string(N2) + ")");
+    if (delta_of[x] >= 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_index " + std::to_string(x) + " repeated");
+    delta_of[x] = (int32_t)i;
+    is_new[x] = series_new[i] ? 1 : 0;
+    if (series_new[i] && b->group_id[i] < TSDB_GROUP_EXCLUDED)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "group id below TSDB_GROUP_EXCLUDED");
+  }
+  std::vector<int32_t> old_of(N2, -1);   // new batch index -> old batch index (-1: a new series)
+  {
+    int64_t o = 0;
+    for (int64_t x = 0; x < N2; x++) {
+      if (is_new[x]) continue;
+      if (o >= N) return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_index implies an old index outside [0, N)");
+      old_of[x] = (int32_t)o++;
+    }
+  }
+  std::vector<int32_t> pos(std::max<int64_t>(N, 1));   // old batch index -> current resident position
+  for (int64_t i = 0; i < N; i++) pos[c->h_orig[i]] = (int32_t)i;
+  // each delta series' rows by base; what happens to them
+  std::vector<int64_t> drow;            // delta rows in staging order: series by series, by base
+  std::vector<int32_t> d0(D), dn(D);
+  std::vector<uint8_t> repl(D, 0);
+  drow.reserve(DR);
+  int64_t n_repl = 0;
+  uint64_t dead_q = 0, dead_v = 0;
+  for (int64_t i = 0; i < D; i++) {
+    const int64_t r0 = b->series_row_ptr[i], r1 = b->series_row_ptr[i + 1];
+    d0[i] = (int32_t)drow.size();
+    dn[i] = (int32_t)(r1 - r0);
+    for (int64_t r = r0; r < r1; r++) drow.push_back(r);
+    std::stable_sort(drow.begin() + d0[i], drow.end(),
+                     [&](int64_t x, int64_t y) { return b->row_base_time[x] < b->row_base_time[y]; });
+    if (series_new[i] || r1 == r0) continue;
+    const int64_t p = pos[old_of[series_index[i]]];
+    if (c->h_srp[p + 1] == c->h_srp[p]) continue;
+    const int64_t last = c->h_srp[p + 1] - 1;
+    const uint32_t first_base = b->row_base_time[drow[d0[i]]];
+    if (first_base < c->h_base[last])
+      return fail(TSDB_E_NOT_IMPLEMENTED,
+                  "tsdbhip_append: a delta row of series " + std::to_string(series_index[i]) + " (base " +
+                      std::to_string(first_base) + ") lies before the series' last resident row (base " +
+                      std::to_string(c->h_base[last]) + "): back-fill and replacing a row that is not the last need a "
+                      "reload (tsdbhip_load of the merged batch)");
+    if (first_base == c->h_base[last]) {
+      repl[i] = 1;
+      n_repl++;
+      dead_q += align16(c->h_qlen[last]);
+      dead_v += align16(c->h_vlen[last]);
+    }
+  }
+  const int64_t NR2 = NR + DR - n_repl;
+  // the groups: resident series keep theirs, new ones take the delta's ids
+  const int64_t G_old = c->n_groups;
+  int32_t maxg = -1;
+  for (int64_t i = 0; i < N; i++)
+    if (c->h_group[i] < G_old) maxg = std::max(maxg, c->h_group[i]);
+  for (int64_t i = 0; i < D; i++)
+    if (series_new[i]) maxg = std::max(maxg, b->group_id[i]);
+  const int64_t G = (int64_t)maxg + 1;
+  auto key = [&](int64_t x) -> int64_t {   // x: new batch index
+    if (is_new[x]) {
+      const int32_t g = b->group_id[delta_of[x]];
+      return g == TSDB_GROUP_EXCLUDED ? G + 1 : g < 0 ? G : g;
+    }
+    const int32_t g = c->h_group[pos[old_of[x]]];
+    return g < G_old ? g : g == G_old ? G : G + 1;
+  };
+  std::vector<int64_t> start(G + 3, 0);
+  for (int64_t x = 0; x < N2; x++) start[key(x) + 1]++;
+  for (int64_t k = 0; k < G + 2; k++) start[k + 1] += start[k];
+  const int64_t n_vis = start[G + 1];
+  // staging of the delta's cells at the blobs' tail, 16-byte aligned
+  std::vector<RowDesc> rd(DR);
+  const uint64_t q0 = align16(c->qual_bytes), v0 = align16(c->val_bytes);   // the tail: where the delta's cells go
+  uint64_t qtot = q0, vtot = v0;
+  for (int64_t k = 0; k < DR; k++) {
+    const int64_t r = drow[k];
+    RowDesc d{};
+    d.base = b->row_base_time[r];
+    d.qlen = (uint32_t)(b->row_qual_off[r + 1] - b->row_qual_off[r]);
+    d.vlen = (uint32_t)(b->row_val_off[r + 1] - b->row_val_off[r]);
+    d.qoff = qtot;
+    d.voff = vtot;
+    qtot += align16(d.qlen);
+    vtot += align16(d.vlen);
+    rd[k] = d;
+  }
+  // (not zero-filled first and not single-threaded: for a large delta this pass is the call's cost)
+  const size_t hq_n = qtot - q0, hv_n = vtot - v0;
+  std::unique_ptr<uint8_t[]> hq(new (std::nothrow) uint8_t[hq_n + 1]), hv(new (std::nothrow) uint8_t[hv_n + 1]);
+  if (!hq || !hv) return fail(TSDB_E_NOMEM, "tsdbhip_append: no host memory to stage the delta's cells");
+  pack_cells(hq.get(), hv.get(), b, drow.data(), rd.data(), DR, q0, v0);
+  HIP_OK(hipSetDevice(c->device));
+  // ---- allocations: nothing of the resident batch is released before the commit ----
+  struct Hold {   // what the call allocated and has not handed to the context
+    DevBuf q, v, v2;
+    ~Hold() { q.release(); v.release(); v2.release(); }
+  } hold;
+  const bool had_val2 = c->val2.p != nullptr;
+  const int64_t reserve = opt(OPT_APPEND_RESERVE) < 0 ? 50 : opt(OPT_APPEND_RESERVE);
+  auto grown = [&](uint64_t need) { return (size_t)(need + need / 100 * reserve + need % 100 * reserve / 100); };
+  const bool grow_q = !c->qual.p || qtot + BLOB_SLACK > c->qual.n, grow_v = !c->val.p || vtot + BLOB_SLACK > c->val.n;
+  auto nomem = [&](hipError_t e) {
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, "tsdbhip_append: the grown blobs do not fit beside the resident ones")
+                                    : fail(TSDB_E_HIP, std::string("tsdbhip_append: ") + hipGetErrorString(e));
+  };
+  hipError_t he;
+  if (grow_q && (he = hold.q.ensure(grown(qtot + BLOB_SLACK))) != hipSuccess) return nomem(he);
+  if (grow_v && (he = hold.v.ensure(grown(vtot + BLOB_SLACK))) != hipSuccess) return nomem(he);
+  const size_t qcap = grow_q ? hold.q.n : c->qual.n;
+  const bool grow_v2 = had_val2 && (grow_q || c->val2.n < qtot + BLOB_SLACK);   // (val2 lives at qualifier offsets)
+  if (grow_v2 && (he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
+  uint8_t* const qp = grow_q ? hold.q.as<uint8_t>() : c->qual.as<uint8_t>();
+  uint8_t* const vp = grow_v ? hold.v.as<uint8_t>() : c->val.as<uint8_t>();
+  HIP_OK(c->ap_rows.ensure(std::max<size_t>(1, (size_t)DR) * sizeof(RowDesc)));
+  HIP_OK(c->ap_ent.ensure((size_t)N2 * sizeof(int4)));
+  HIP_OK(c->ap_touch.ensure((size_t)D * 4));
+  HIP_OK(c->ap_stage.ensure((size_t)N2 * sizeof(int4) + (size_t)D * 4));
+  HIP_OK(c->rows2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  HIP_OK(c->srp2.ensure((size_t)(N2 + 1) * 8));
+  HIP_OK(c->gid2.ensure((size_t)N2 * 4));
+  HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  HIP_OK(c->hint.ensure(std::max<int64_t>(1, DR)));
+  HIP_OK(c->ilist.ensure(std::max<int64_t>(1, DR) * 4));
+  HIP_OK(c->icnt.ensure(32 * 4));
+  // val2 for the delta's index pass, by finish_load's rule; a copy the resident rows lacked is
+  // allocated at the qualifier blob's capacity (resident rows never read it)
+  const bool generic = opt_is(OPT_INDEX_GENERIC, 1);
+  bool fused = false;
+  uint8_t* v2p = grow_v2 ? hold.v2.as<uint8_t>() : c->val2.as<uint8_t>();   // (null when there was none)
+  if (!generic) {
+    size_t fr = 0, tot = 0;
+    if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > qcap + ((size_t)8 << 30)) {
+      if (!v2p) {
+        if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
+        v2p = hold.v2.as<uint8_t>();
+      }
+      fused = true;
+    }
+  }
+  // ---- queued work: the cells, the delta's index, the merge-gather ----
+  hipEvent_t* ev = c->ev;
+  // option TRACE: the stages by hipEvents of the call's own (stream time between stage ends, the
+  // host work in between included), on stderr
+  struct Trace {
+    hipEvent_t e[6] = {};
+    bool on = false;
+    ~Trace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
+  } tr;
+  if (opt_is(OPT_TRACE, 1)) {
+    tr.on = true;
+    for (auto& x : tr.e) HIP_OK(hipEventCreate(&x));
+  }
+  auto mark = [&](int i) { return tr.on ? hipEventRecord(tr.e[i], c->stream) : hipSuccess; };
+  HIP_OK(mark(0));
+  if (grow_q) {
+    if (c->qual_bytes) HIP_OK(hipMemcpyAsync(qp, c->qual.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(qp + c->qual_bytes, 0, qcap - c->qual_bytes, c->stream));
+  }
+  if (grow_v2 && c->qual_bytes)
+    HIP_OK(hipMemcpyAsync(hold.v2.p, c->val2.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (grow_v) {
+    if (c->val_bytes) HIP_OK(hipMemcpyAsync(vp, c->val.p, c->val_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(vp + c->val_bytes, 0, hold.v.n - c->val_bytes, c->stream));
+  }
+  HIP_OK(mark(1));
+  if (hq_n) HIP_OK(h2d(c, qp + q0, hq.get(), hq_n, c->stream));
+  if (hv_n) HIP_OK(h2d(c, vp + v0, hv.get(), hv_n, c->stream));
+  if (!grow_q) HIP_OK(hipMemsetAsync(qp + qtot, 0, BLOB_SLACK, c->stream));   // (the slack past the new end reads as zeros)
+  if (!grow_v) HIP_OK(hipMemsetAsync(vp + vtot, 0, BLOB_SLACK, c->stream));
+  if (DR) HIP_OK(hipMemcpyAsync(c->ap_rows.p, rd.data(), (size_t)DR * sizeof(RowDesc), hipMemcpyHostToDevice, c->stream));
+  // the entries of the new order: a counting sort by (key, new batch index)
+  int4* ent = reinterpret_cast<int4*>(c->ap_stage.p);
+  int32_t* touched = reinterpret_cast<int32_t*>(ent + N2);
+  int64_t n_touched = 0;
+  std::vector<int64_t> n_orig(N2), n_srp(N2 + 1, 0);
+  std::vector<int32_t> n_group(N2);
+  {
+    std::vector<int64_t> cur(start.begin(), start.end() - 1);
+    for (int64_t x = 0; x < N2; x++) {
+      const int64_t k = key(x), i = cur[k]++;
+      const int32_t di = delta_of[x];
+      ent[i].x = is_new[x] ? -1 : pos[old_of[x]];
+      ent[i].y = (int32_t)k;
+      ent[i].z = di >= 0 ? d0[di] : 0;
+      ent[i].w = di >= 0 ? (dn[di] | (repl[di] ? APPEND_REPLACE : 0)) : 0;
+      n_orig[i] = x;
+      n_group[i] = (int32_t)k;
+      if (di >= 0 && dn[di] > 0) touched[n_touched++] = (int32_t)i;
+    }
+    for (int64_t i = 0; i < N2; i++) {
+      const int64_t res = ent[i].x >= 0 ? c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x] : 0;
+      n_srp[i + 1] = n_srp[i] + res - ((ent[i].w & APPEND_REPLACE) ? 1 : 0) + (ent[i].w & ~APPEND_REPLACE);
+    }
+  }
+  if (n_srp[N2] != NR2) return fail(TSDB_E_HIP, "tsdbhip_append: row count mismatch (internal)");
+  HIP_OK(hipMemcpyAsync(c->ap_ent.p, ent, (size_t)N2 * sizeof(int4), hipMemcpyHostToDevice, c->stream));
+  if (n_touched)
+    HIP_OK(hipMemcpyAsync(c->ap_touch.p, touched, (size_t)n_touched * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));   // (rd, hq, hv are pageable: staged before they leave scope)
+  // index only the delta: its descriptors in their own array, the blob base pointers as they are
+  HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
+  const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
+  RowDesc* drows = c->ap_rows.as<RowDesc>();
+  HIP_OK(mark(2));
+  HIP_OK(hipEventRecord(ev[2], c->stream));
+  IndexClasses ik{};
+  uint32_t idx_cnt[16] = {};
+  if (DR) {
+    if (fused)
+      HIP_OK(index_fused(qp, vp, v2p, drows, ib, DR, c->err.as<int32_t>(), &ik, c->stream));
+    else
+      HIP_OK(index_classes(qp, drows, ib, DR, &ik, c->stream));
+    if (!fused && ik.vle_capable && !generic && !v2p) {
+      if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
+      v2p = hold.v2.as<uint8_t>();
+    }
+    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, ib, ik, DR, c->err.as<int32_t>(), generic, c->stream));
+    if (!generic) {
+      std::memcpy(idx_cnt, ik.cnt, sizeof(idx_cnt));
+      if (!fused) idx_cnt[IDX_C_FAIL] = 0;
+      if (!fused && ik.short_rows)
+        HIP_OK(hipMemcpyAsync(&idx_cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  HIP_OK(hipEventRecord(ev[3], c->stream));
+  float t_index = 0;
+  // does a delta row need the int16 copy?  (known from the indexed descriptors)
+  bool need_val2 = false;
+  if (DR) {
+    HIP_OK(hipMemcpyAsync(rd.data(), drows, (size_t)DR * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&t_index, ev[2], ev[3]);
+    for (const RowDesc& d : rd)
+      if ((d.flags & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2)) { need_val2 = true; break; }
+    if (need_val2 && generic) {   // test hook: the sequential path writes the copy in a second pass
+      if (!v2p) {
+        if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
+        v2p = hold.v2.as<uint8_t>();
+      }
+      HIP_OK(hipEventRecord(ev[2], c->stream));
+      HIP_OK(index_rows(qp, vp, v2p, drows, ib, ik, DR, c->err.as<int32_t>(), true, c->stream));
+      HIP_OK(hipEventRecord(ev[3], c->stream));
+      HIP_OK(hipStreamSynchronize(c->stream));
+      float t2 = 0;
+      (void)hipEventElapsedTime(&t2, ev[2], ev[3]);
+      t_index += t2;
+    }
+  }
+  HIP_OK(mark(3));
+  AppendParams ap{};
+  ap.ent = c->ap_ent.as<int4>();
+  ap.srp_old = c->srp.as<int64_t>();
+  ap.rows_old = c->rows.as<RowDesc>();
+  ap.rows_delta = drows;
+  ap.n_series = N2;
+  ap.n_rows = NR2;
+  ap.srp_new = c->srp2.as<int64_t>();
+  ap.rows_new = c->rows2.as<RowDesc>();
+  ap.gid_new = c->gid2.as<int32_t>();
+  HIP_OK(append_scan(ap, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(launch_append(ap, c->stream));
+  HIP_OK(launch_append_recede(ap, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
+  HIP_OK(mark(4));
+  if (NR2)
+    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(mark(5));
+  std::vector<uint32_t> n_base(NR2), n_ndp(NR2), n_qlen(NR2), n_vlen(NR2), n_flags(NR2);
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (tr.on) {
+    float t[5] = {};
+    for (int i = 0; i < 5; i++) (void)hipEventElapsedTime(&t[i], tr.e[i], tr.e[i + 1]);
+    std::fprintf(stderr, "[trace append] grow_copy %.3f upload %.3f index %.3f scan_gather %.3f desc_download %.3f ms\n",
+                 t[0], t[1], t[2], t[3], t[4]);
+  }
+  {
+    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
+    for (int64_t r = 0; r < NR2; r++) {
+      n_base[r] = back[r].base;
+      n_ndp[r] = back[r].ndp;
+      n_qlen[r] = back[r].qlen;
+      n_vlen[r] = back[r].vlen;
+      n_flags[r] = back[r].flags;
+    }
+  }
+  // ---- commit: from here on the context holds the merged batch ----
+  std::swap(c->rows, c->rows2);
+  std::swap(c->srp, c->srp2);
+  std::swap(c->gid, c->gid2);
+  if (grow_q) std::swap(c->qual, hold.q);
+  if (grow_v) std::swap(c->val, hold.v);
+  if (had_val2 ? grow_v2 : (hold.v2.p && need_val2)) std::swap(c->val2, hold.v2);
+  // (a copy allocated for the index pass that no delta row needs goes with `hold`)
+  c->qual_bytes = qtot;
+  c->val_bytes = vtot;
+  c->qual_dead += dead_q;
+  c->val_dead += dead_v;
+  c->h_srp.swap(n_srp);
+  c->h_base.swap(n_base);
+  c->h_ndp.swap(n_ndp);
+  c->h_qlen.swap(n_qlen);
+  c->h_vlen.swap(n_vlen);
+  c->h_flags.swap(n_flags);
+  c->h_orig.swap(n_orig);
+  c->h_group.swap(n_group);
+  c->n_series_loaded = N2;
+  c->n_rows_loaded = NR2;
+  c->n_series = n_vis;
+  c->n_rows = c->h_srp[n_vis];
+  c->n_groups = G;
+  c->max_series_rows = 0;
+  for (int64_t i = 0; i < n_vis; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
+  if (n_vis == N2) {
+    c->h_excl.clear();
+  } else {
+    c->h_excl.assign(N2, 0);
+    for (int64_t i = n_vis; i < N2; i++) c->h_excl[c->h_orig[i]] = 1;
+  }
+  // tsdbhip_load_cells' compaction errors: renumbered; an entry whose row the delta brings anew
+  // (the scan now returned that row) is dropped
+  if (!c->cmp_errs.empty()) {
+    std::vector<int64_t> new_of(std::max<int64_t>(N, 1));
+    for (int64_t x = 0; x < N2; x++)
+      if (old_of[x] >= 0) new_of[old_of[x]] = x;
+    std::vector<tsdbhip_ctx::CmpErr> kept;
+    for (auto e : c->cmp_errs) {
+      if (e.series < 0 || e.series >= N) continue;
+      const int64_t x = new_of[e.series];
+      const int32_t di = delta_of[x];
+      bool replaced = false;
+      if (di >= 0)
+        for (int64_t k = d0[di]; k < d0[di] + dn[di]; k++) replaced |= (int64_t)b->row_base_time[drow[k]] == e.base;
+      if (replaced) continue;
+      e.series = x;
+      kept.push_back(e);
+    }
+    c->cmp_errs.swap(kept);
+  }
+  std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
+  c->idx_fused = fused;
+  c->index_ms = t_index;
+  // what a load invalidates of the state that depends on the rows, the series' order or groups
+  c->none_tiles_ready = false;
+  c->acct_valid = false;
+  c->seqd_valid = false;
+  c->row_ser_valid = false;
+  c->n_grouped = -1;
+  c->mdp_valid = false;
+  c->ro_meta_valid = false;
+  c->lc_valid = false;
+  c->calc_valid = false;
+  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the batch they came from)
+  c->pg.cells = 0;
+  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  const int rc = finish_classes(c);
+  fill_info(K, DR - n_repl, n_repl, grow_q || grow_v);
+  return rc;
 }
 
 extern "C" int tsdbhip_batch_sizes(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_rows, uint64_t* qual_bytes,
@@ -6799,5 +7255,20 @@ hipError_t h2d(tsdbhip_ctx* c, void* dst, const void* src, size_t n, hipStream_t
     c->up_busy[b] = true;
   }
   return hipSuccess;
+}
+
+void pack_cells(uint8_t* dq, uint8_t* dv, const tsdbhip_batch* b, const int64_t* row, const RowDesc* rd, int64_t n,
+                uint64_t q0, uint64_t v0) {
+  const int64_t work = n ? (int64_t)((rd[n - 1].qoff - q0) + (rd[n - 1].voff - v0)) : 0;   // bytes, about
+  par_groups(n, work, [&](int64_t k) {
+    const int64_t r = row[k];
+    const RowDesc& d = rd[k];
+    uint8_t* q = dq + (d.qoff - q0);
+    uint8_t* v = dv + (d.voff - v0);
+    if (d.qlen) std::memcpy(q, b->qual + b->row_qual_off[r], d.qlen);
+    if (d.vlen) std::memcpy(v, b->val + b->row_val_off[r], d.vlen);
+    std::memset(q + d.qlen, 0, (size_t)(align16(d.qlen) - d.qlen));
+    std::memset(v + d.vlen, 0, (size_t)(align16(d.vlen) - d.vlen));
+  });
 }
 }  // namespace tsdb

@@ -517,6 +517,27 @@ struct RegroupParams {
 };
 hipError_t regroup_scan(const RegroupParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_regroup(const RegroupParams& p, hipStream_t s);
+// tsdbhip_append (k_append.hip): the resident RowDescs merged with a delta's, in a new series
+// order.  Entry i of `ent` is the series at new position i: x = its current resident position
+// (-1: a series not resident so far), y = its group word, z = its first row in `rows_delta`
+// (the series' delta rows are contiguous there, sorted by base time), w = its delta row count,
+// with APPEND_REPLACE set when the first of them replaces the series' last resident row.
+static constexpr int32_t APPEND_REPLACE = (int32_t)0x80000000u;
+struct AppendParams {
+  const int4* ent;            // [n_series]
+  const int64_t* srp_old;     // [n_series_old + 1] current series_row_ptr (every loaded series)
+  const RowDesc* rows_old;    // [n_rows_old]
+  const RowDesc* rows_delta;  // [n_delta] the delta's descriptors after their index pass
+  int64_t n_series, n_rows;   // counts AFTER the append (the excluded tail included)
+  int64_t* srp_new;           // [n_series + 1]
+  RowDesc* rows_new;          // [n_rows]
+  int32_t* gid_new;           // [n_series]
+};
+hipError_t append_scan(const AppendParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_append(const AppendParams& p, hipStream_t s);
+// k_recede over the series at new positions touched[0 .. n): ROW_UNSORTED on delta rows only
+hipError_t launch_append_recede(const AppendParams& p, const int32_t* touched, int64_t n, const uint8_t* qual,
+                                hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

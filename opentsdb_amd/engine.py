@@ -35,14 +35,14 @@ EXPORTS = [
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
-    "tsdbhip_regroup",
+    "tsdbhip_regroup", "tsdbhip_append",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
 OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-           "HIST_WS", "HIST_LAYOUT", "TRACE", "DBG"]
+           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "TRACE", "DBG"]
 
 IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
@@ -118,6 +118,7 @@ def lib():
         L.tsdbhip_host_free.restype = None
         L.tsdbhip_load.argtypes = [vp, C.POINTER(abi.Batch)]
         L.tsdbhip_regroup.argtypes = [vp, C.c_void_p, C.c_int64]
+        L.tsdbhip_append.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.AppendInfo)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
         L.tsdbhip_batch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]
@@ -378,6 +379,21 @@ class Engine:
         if ids.ndim != 1:
             raise ValueError("group_ids must be one-dimensional")
         _check(lib().tsdbhip_regroup(self.ctx, ids.ctypes.data, len(ids)))
+
+    def append(self, delta: abi.HostBatch, series_index, series_new) -> abi.AppendInfo:
+        """tsdbhip_append: the delta's rows appended to the resident batch (a row with the base
+        time of its series' last resident row replaces it).  series_index[i] is delta series i's
+        index in the batch after the append, series_new[i] marks a series not resident so far;
+        from then on Engine.regroup's ids are in the new index space."""
+        idx = np.ascontiguousarray(series_index, dtype=np.int64)
+        new = np.ascontiguousarray(np.asarray(series_new) != 0, dtype=np.uint8)
+        if idx.ndim != 1 or idx.shape != new.shape or len(idx) != delta.n_series:
+            raise ValueError("series_index and series_new need one entry a delta series")
+        info = abi.AppendInfo()
+        # (an empty array's data pointer may be null: the library wants non-null pointers only with series)
+        _check(lib().tsdbhip_append(self.ctx, C.byref(delta.c), idx.ctypes.data if len(idx) else None,
+                                    new.ctypes.data if len(new) else None, C.byref(info)))
+        return info
 
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""

@@ -600,6 +600,37 @@ class ResidentSpans:
             ids[i] = g
         return ids, keys
 
+    def extend(self, scan_end_s: int, rescan_from_s: int | None = None):
+        """Move the resident range's end to scan_end_s without a reload (Engine.append,
+        tsdbhip_append): rescan [rescan_from_s, scan_end_s) -- by default from the largest
+        resident row base time, the live hour, whose row the store may have rewritten since --
+        and hand the engine that delta.  A rescanned row replaces the resident row of the same
+        base time; series the scan meets for the first time are inserted where SpanCmp order puts
+        them, excluded until the next run() regroups.  Returns the engine's abi.AppendInfo."""
+        if scan_end_s < self.scan_end_s:
+            raise ValueError(f"the resident range ends at {self.scan_end_s}: it cannot shrink to {scan_end_s}")
+        if rescan_from_s is None:
+            rescan_from_s = max((rows[-1][0] for _, rows in self.spans if rows), default=self.scan_end_s)
+        delta = self.store.scan(self.metric, rescan_from_s, scan_end_s)
+        old = dict(zip(self.span_keys, self.spans))
+        dkeys = {sk for sk, _ in delta}
+        # SpanCmp order over the union of the keys: the store's own series order
+        merged_keys = [sk for sk in self.store.series(self.metric) if sk in old or sk in dkeys]
+        index_of = {sk: i for i, sk in enumerate(merged_keys)}
+        series_index = [index_of[sk] for sk, _ in delta]
+        series_new = [sk not in old for sk, _ in delta]
+        info = self.engine.append(make_batch(delta, [abi.GROUP_EXCLUDED] * len(delta)), series_index, series_new)
+        drows = dict(delta)
+        spans = []
+        for sk in merged_keys:
+            by_base = {r[0]: r for r in (old[sk][1] if sk in old else [])}
+            by_base.update({r[0]: r for r in drows.get(sk, [])})   # the delta wins
+            spans.append((sk, [by_base[b] for b in sorted(by_base)]))
+        self.spans = spans
+        self.span_keys = merged_keys
+        self.scan_end_s = scan_end_s
+        return info
+
     def run(self, query: TsdbQuery):
         """DataPoints[] of the query, keyed as TsdbQuery._run_raw keys them."""
         if query.store is not self.store or query.metric != self.metric:
