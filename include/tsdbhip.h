@@ -199,7 +199,8 @@ const char* tsdbhip_last_error(void);
  * CMP_ROWS, CMP_ONEPASS, PCT_ROWS, PCT_KEYS,
  * PCT_VONLY, PCT_V6, SEL_FUSED, SEL_COLS, SEL_WIN, SEL_WAVE, SEL_REG, SELOPS, RAW_LERPW,
  * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT,
- * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit), TRACE, DBG
+ * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit),
+ * REGULAR (0: the regular tile lists through the ordinary streaming kernel, qualifiers read), TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
  * its production choice, which is every option's initial state.  The library reads no
  * environment variable: an inherited environment cannot change its kernels.  DBG is honoured
@@ -820,6 +821,13 @@ int tsdbhip_sync(tsdbhip_ctx* ctx);
  * batch, rows in resident order -- datapoints, RowDesc flags, exactness-certificate lsb and
  * max |value|.  Any pointer may be null. */
 int tsdbhip_debug_rows(tsdbhip_ctx* ctx, uint32_t* ndp, uint32_t* flags, int32_t* lsb, double* absmax);
+
+/* Test hook (no reference counterpart): the regular rows of the resident batch.  first_step:
+ * [rows][2], a row's {first offset (s), step (s)} when its datapoints sit at first + i * step
+ * (2-byte qualifiers only, well-formed, sorted; a one-point row has step 1), else step 0;
+ * list_tiles[2]: the tiles on each streaming class's regular list; *launched: the tiles the
+ * last query ran through the values-only form of k_fast.  Any pointer may be null. */
+int tsdbhip_debug_regular(tsdbhip_ctx* ctx, uint32_t* first_step, int64_t* list_tiles, int64_t* launched);
 
 /* Test hook (no reference counterpart): the routes the last load's index took.  cnt[0..10] are
  * the rows of each index class (0: the sequential kernel's, 1 + 5 (4-byte qualifiers) + value

@@ -396,6 +396,8 @@ struct tsdbhip_ctx {
   uint64_t qual_bytes = 0, val_bytes = 0;
   DevBuf rows, srp, qual, val, gid;
   DevBuf val2;                         // int16 copy of vle-integer values (k_index), at qualifier offsets
+  DevBuf reg;                          // [n_rows] RegRow beside rows[]: the regular rows' {first, step} (k_index)
+  DevBuf reg2, ap_reg;                 // regroup / append: the gather's destination (swapped with reg); the delta's entries
   DevBuf hint, ilist, icnt;            // k_index scratch: row classes, rows by class, class counts
   // tsdbhip_regroup: every loaded series stays resident; those a regroup excluded sit after the
   // visible ones -- positions [n_series, n_series_loaded) of rows / srp / gid and of the host
@@ -419,6 +421,7 @@ struct tsdbhip_ctx {
   std::vector<uint32_t> h_ndp;         // [n_rows]
   std::vector<uint32_t> h_qlen, h_vlen;
   std::vector<uint32_t> h_flags;       // [n_rows] RowDesc.flags after k_index
+  std::vector<RegRow> h_reg;           // [n_rows] host mirror of reg
   std::vector<int32_t> h_group;        // [n_series] group of sorted position
   std::vector<int64_t> h_orig;         // [n_series] original batch index of sorted position
   // tiles over groups
@@ -474,10 +477,14 @@ struct tsdbhip_ctx {
   // tile lists by k_fast row class (built at load): [class A / class B][walker / short /
   // rows], and the tiles of neither class (general kernel only).  Short = one row per series
   // of at most CH datapoints (k_short); rows = several rows per series, none over CH (k_rows).
-  std::vector<int32_t> tl[2][3], tl_other;
+  // [3]: the walker tiles whose every row is regular (RegRow), for a class k_fast has a REG form
+  // of (2-byte qualifiers, 4- or 8-byte values); they are not on [0]
+  std::vector<int32_t> tl[2][4], tl_other;
   DevBuf d_tl, d_tl_n, r1a, r1b, r3a, r3b, r2, r_n;   // device copies; k_short / k_rows / k_fast redo lists
   DevBuf hw_mark;                                      // k_hwin: a tile is on the redo list (one word a tile)
-  int64_t tl_off[7] = {};
+  int64_t tl_off[9] = {};                              // 3 cls + j (j < 3), 6: tl_other, 7 + cls: tl[cls][3]
+  int64_t reg_launched = 0;                            // tiles the last query launched through k_fast's REG form
+  int reg_cls = 0;                                     // ... bit cls: that class's regular list went through it
   bool fast_used = false;
   HostBuf h_stage;   // collect(): the dense [G][K] values and flags, page-locked
   HostBuf h_small;   // collect(): the group activity flags, error code and hand-back count, page-locked
@@ -504,6 +511,7 @@ struct tsdbhip_ctx {
   int64_t seqd_ss = 0, seqd_se = 0;
   int64_t acct_ss = 0, acct_se = 0, acct_dps = 0, acct_bytes = 0;
   bool acct_none = false;
+  int acct_reg = 0;                    // account()'s `reg` of the cached figures
   // rollup generation: scratch and the per-function cells of the last tsdbhip_rollup_run
   DevBuf ro_allint, ro_ord, ro_orig, ro_cnt, ro_vsz, ro_coff, ro_voff;
   DevBuf ro_agg, ro_pres;              // fused rollup pass: [4][series][K] values, [series][K] presence
@@ -645,7 +653,7 @@ const char* const kOptNames[OPT_COUNT] = {
     "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "TRACE", "DBG"};
+    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "TRACE", "DBG"};
 int opt_index(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < OPT_COUNT; i++)
@@ -824,7 +832,8 @@ extern "C" int tsdbhip_init(int device, tsdbhip_ctx** out) {
 
 static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
-                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch})
+                    &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
+                    &c->reg, &c->reg2, &c->ap_reg})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -987,21 +996,28 @@ static int build_tiles(tsdbhip_ctx* c) {
     bool chunk = true;   // every row one chunk
     for (int64_t r = r0; r < r1 && chunk; r++) chunk = c->h_ndp[r] <= (uint32_t)CH_ROWS;
     const bool shrt = chunk && r1 - r0 == c->te[t] - c->tb[t];
-    c->tl[cls][shrt ? 1 : (chunk && c->te[t] - c->tb[t] <= 64) ? 2 : 0].push_back((int32_t)t);
+    int j = shrt ? 1 : (chunk && c->te[t] - c->tb[t] <= 64) ? 2 : 0;
+    if (j == 0) {   // the walker's tile: on the regular list when every row is regular (the granularity is the tile)
+      const int qw = cls ? c->fast_qw2 : c->fast_qw, vl = cls ? c->fast_vl2 : c->fast_vl;
+      bool reg = qw == 2 && (vl == 4 || vl == 8);
+      for (int64_t r = r0; r < r1 && reg; r++) reg = c->h_reg[r].step != 0;
+      if (reg) j = 3;
+    }
+    c->tl[cls][j].push_back((int32_t)t);
   }
   {
     std::vector<int32_t> all, cnt;
-    const std::vector<int32_t>* parts[7] = {&c->tl[0][0], &c->tl[0][1], &c->tl[0][2], &c->tl[1][0],
-                                            &c->tl[1][1], &c->tl[1][2], &c->tl_other};
-    for (int i = 0; i < 7; i++) {
+    const std::vector<int32_t>* parts[9] = {&c->tl[0][0], &c->tl[0][1], &c->tl[0][2], &c->tl[1][0], &c->tl[1][1],
+                                            &c->tl[1][2], &c->tl_other,  &c->tl[0][3], &c->tl[1][3]};
+    for (int i = 0; i < 9; i++) {
       c->tl_off[i] = (int64_t)all.size();
       all.insert(all.end(), parts[i]->begin(), parts[i]->end());
       cnt.push_back((int32_t)parts[i]->size());
     }
     HIP_OK(c->d_tl.ensure(std::max<size_t>(1, all.size()) * 4));
-    HIP_OK(c->d_tl_n.ensure(7 * 4));
+    HIP_OK(c->d_tl_n.ensure(9 * 4));
     if (!all.empty()) HIP_OK(hipMemcpy(c->d_tl.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(c->d_tl_n.p, cnt.data(), 7 * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(c->d_tl_n.p, cnt.data(), 9 * 4, hipMemcpyHostToDevice));
   }
   HIP_OK(c->d_tb.ensure(nt * 8));
   HIP_OK(c->d_te.ensure(nt * 8));
@@ -1091,6 +1107,8 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   // the int16 copy of 1-2-byte integer values (val2, k_short / k_fast's vle rows) is written by
   // the class kernels of the 2-byte-qualifier integer classes, allocated when such rows exist
   c->val2.release();
+  HIP_OK(c->reg.ensure(std::max<size_t>(1, (size_t)c->n_rows) * sizeof(RegRow)));
+  RegRow* const regp = c->reg.as<RegRow>();
   // val2 allocated up front when it fits beside the batch with room to spare: the short rows are
   // then indexed by the classifying pass itself (index_fused, no separate k_index_hint); else the
   // classes first, val2 only when some row can need it (a 216-GB store has no room for a spare 72)
@@ -1106,21 +1124,24 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   HIP_OK(hipEventRecord(c->ev[0], c->stream));
   IndexClasses ik;
   if (fused)
-    HIP_OK(index_fused(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), ib,
+    HIP_OK(index_fused(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), regp, ib,
                        c->n_rows, c->err.as<int32_t>(), &ik, c->stream));
   else
     HIP_OK(index_classes(c->qual.as<uint8_t>(), c->rows.as<RowDesc>(), ib, c->n_rows, &ik, c->stream));
   HIP_OK(hipEventRecord(c->ev[2], c->stream));
   if (!fused && ik.vle_capable && !generic) HIP_OK(c->val2.ensure(c->qual_bytes + BLOB_SLACK));
   HIP_OK(hipEventRecord(c->ev[3], c->stream));   // (the allocation is not index time)
-  HIP_OK(index_rows(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), ib, ik,
+  HIP_OK(index_rows(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), regp, ib, ik,
                     c->n_rows, c->err.as<int32_t>(), generic, c->stream));
   if (c->max_series_rows > 1)   // (rows going back in time need two rows of one series)
-    HIP_OK(index_recede(c->rows.as<RowDesc>(), c->srp.as<int64_t>(), c->qual.as<uint8_t>(), c->n_series, c->stream));
+    HIP_OK(index_recede(c->rows.as<RowDesc>(), regp, c->srp.as<int64_t>(), c->qual.as<uint8_t>(), c->n_series, c->stream));
   HIP_OK(hipEventRecord(c->ev[1], c->stream));
   std::vector<RowDesc> back(c->n_rows);
   if (c->n_rows)
     HIP_OK(hipMemcpyAsync(back.data(), c->rows.p, c->n_rows * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  c->h_reg.resize(c->n_rows);
+  if (c->n_rows)
+    HIP_OK(hipMemcpyAsync(c->h_reg.data(), regp, c->n_rows * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
   // tsdbhip_debug_index: the class counts; k_index_short's hand-backs are counted on the device
   // only when it ran from the hints (index_fused has read its own), so that word rides along
   std::memset(c->idx_cnt, 0, sizeof(c->idx_cnt));
@@ -1144,7 +1165,7 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   } else if (generic) {   // test hook: the sequential path writes the copy in a second pass
     HIP_OK(c->val2.ensure(c->qual_bytes + BLOB_SLACK));
     HIP_OK(hipEventRecord(c->ev[2], c->stream));
-    HIP_OK(index_rows(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), ib,
+    HIP_OK(index_rows(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), regp, ib,
                       ik, c->n_rows, c->err.as<int32_t>(), true, c->stream));
     HIP_OK(hipEventRecord(c->ev[3], c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -2601,6 +2622,9 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   rp.srp_new = c->srp2.as<int64_t>();
   rp.rows_new = c->rows2.as<RowDesc>();
   rp.gid_new = c->gid2.as<int32_t>();
+  HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RegRow)));
+  rp.reg_old = c->reg.as<RegRow>();
+  rp.reg_new = c->reg2.as<RegRow>();
   HIP_OK(regroup_scan(rp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
   HIP_OK(launch_regroup(rp, c->stream));
   // host mirrors in the new order: series_row_ptr from the old one while the device works, the
@@ -2610,6 +2634,8 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RowDesc)));
   if (NR)
     HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  std::vector<RegRow> n_reg(NR);
+  if (NR) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
   std::vector<int64_t> n_srp(N + 1, 0);
   for (int64_t i = 0; i < N; i++) n_srp[i + 1] = n_srp[i] + (c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x]);
   std::vector<uint32_t> n_base(NR), n_ndp(NR), n_qlen(NR), n_vlen(NR), n_flags(NR);
@@ -2626,6 +2652,8 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   }
   // commit: from here on the context holds the new grouping
   std::swap(c->rows, c->rows2);
+  std::swap(c->reg, c->reg2);
+  c->h_reg.swap(n_reg);
   std::swap(c->srp, c->srp2);
   std::swap(c->gid, c->gid2);
   c->h_srp.swap(n_srp);
@@ -2839,6 +2867,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   uint8_t* const qp = grow_q ? hold.q.as<uint8_t>() : c->qual.as<uint8_t>();
   uint8_t* const vp = grow_v ? hold.v.as<uint8_t>() : c->val.as<uint8_t>();
   HIP_OK(c->ap_rows.ensure(std::max<size_t>(1, (size_t)DR) * sizeof(RowDesc)));
+  HIP_OK(c->ap_reg.ensure(std::max<size_t>(1, (size_t)DR) * sizeof(RegRow)));
+  HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RegRow)));
   HIP_OK(c->ap_ent.ensure((size_t)N2 * sizeof(int4)));
   HIP_OK(c->ap_touch.ensure((size_t)D * 4));
   HIP_OK(c->ap_stage.ensure((size_t)N2 * sizeof(int4) + (size_t)D * 4));
@@ -2928,20 +2958,21 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
   const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
   RowDesc* drows = c->ap_rows.as<RowDesc>();
+  RegRow* dreg = c->ap_reg.as<RegRow>();
   HIP_OK(mark(2));
   HIP_OK(hipEventRecord(ev[2], c->stream));
   IndexClasses ik{};
   uint32_t idx_cnt[16] = {};
   if (DR) {
     if (fused)
-      HIP_OK(index_fused(qp, vp, v2p, drows, ib, DR, c->err.as<int32_t>(), &ik, c->stream));
+      HIP_OK(index_fused(qp, vp, v2p, drows, dreg, ib, DR, c->err.as<int32_t>(), &ik, c->stream));
     else
       HIP_OK(index_classes(qp, drows, ib, DR, &ik, c->stream));
     if (!fused && ik.vle_capable && !generic && !v2p) {
       if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
       v2p = hold.v2.as<uint8_t>();
     }
-    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, ib, ik, DR, c->err.as<int32_t>(), generic, c->stream));
+    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, dreg, ib, ik, DR, c->err.as<int32_t>(), generic, c->stream));
     if (!generic) {
       std::memcpy(idx_cnt, ik.cnt, sizeof(idx_cnt));
       if (!fused) idx_cnt[IDX_C_FAIL] = 0;
@@ -2965,7 +2996,7 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
         v2p = hold.v2.as<uint8_t>();
       }
       HIP_OK(hipEventRecord(ev[2], c->stream));
-      HIP_OK(index_rows(qp, vp, v2p, drows, ib, ik, DR, c->err.as<int32_t>(), true, c->stream));
+      HIP_OK(index_rows(qp, vp, v2p, drows, dreg, ib, ik, DR, c->err.as<int32_t>(), true, c->stream));
       HIP_OK(hipEventRecord(ev[3], c->stream));
       HIP_OK(hipStreamSynchronize(c->stream));
       float t2 = 0;
@@ -2984,12 +3015,17 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   ap.srp_new = c->srp2.as<int64_t>();
   ap.rows_new = c->rows2.as<RowDesc>();
   ap.gid_new = c->gid2.as<int32_t>();
+  ap.reg_old = c->reg.as<RegRow>();
+  ap.reg_delta = dreg;
+  ap.reg_new = c->reg2.as<RegRow>();
   HIP_OK(append_scan(ap, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
   HIP_OK(launch_append(ap, c->stream));
   HIP_OK(launch_append_recede(ap, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
   HIP_OK(mark(4));
   if (NR2)
     HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  std::vector<RegRow> n_reg(NR2);
+  if (NR2) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR2 * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(mark(5));
   std::vector<uint32_t> n_base(NR2), n_ndp(NR2), n_qlen(NR2), n_vlen(NR2), n_flags(NR2);
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -3011,6 +3047,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   }
   // ---- commit: from here on the context holds the merged batch ----
   std::swap(c->rows, c->rows2);
+  std::swap(c->reg, c->reg2);
+  c->h_reg.swap(n_reg);
   std::swap(c->srp, c->srp2);
   std::swap(c->gid, c->gid2);
   if (grow_q) std::swap(c->qual, hold.q);
@@ -3218,6 +3256,27 @@ extern "C" int tsdbhip_debug_index(tsdbhip_ctx* c, uint32_t cnt[16], int* fused)
 }
 
 // Test hook: the per-row facts k_index derived (RowDesc.ndp / flags / lsb / absmax).
+// Test hook: the visible rows' RegRow entries (first_step: [n_rows][2] uint32), the tiles on each
+// class's regular list (list_tiles[2]) and the tiles the last query launched through k_fast's REG
+// form.  Null pointers are skipped.
+extern "C" int tsdbhip_debug_regular(tsdbhip_ctx* c, uint32_t* first_step, int64_t* list_tiles, int64_t* launched) {
+  MD_REFUSE(c, "tsdbhip_debug_regular");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  CtxLock lk(c);
+  HIP_OK(hipSetDevice(c->device));
+  if (first_step && c->n_rows) {   // (the device array; the host mirror decides the lists below)
+    static_assert(sizeof(RegRow) == 2 * sizeof(uint32_t), "RegRow is {first, step}");
+    HIP_OK(hipMemcpy(first_step, c->reg.p, c->n_rows * sizeof(RegRow), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < c->n_rows; r++)
+      if (first_step[2 * r] != c->h_reg[r].first || first_step[2 * r + 1] != c->h_reg[r].step)
+        return fail(TSDB_E_HIP, "tsdbhip_debug_regular: the host mirror differs from the device array");
+  }
+  if (list_tiles)
+    for (int cls = 0; cls < 2; cls++) list_tiles[cls] = (int64_t)c->tl[cls][3].size();
+  if (launched) *launched = c->reg_launched;
+  return 0;
+}
+
 extern "C" int tsdbhip_debug_rows(tsdbhip_ctx* c, uint32_t* ndp, uint32_t* flags, int32_t* lsb, double* absmax) {
   MD_REFUSE(c, "tsdbhip_debug_rows");
   if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
@@ -3705,7 +3764,7 @@ int hwin_slots(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, bool for_m
       P.seq_dense || P.raw || P.anchored || P.none || P.f == F_SEL || !c->fast_qw || !c->tl_other.empty())
     return 0;
   for (int cls = 0; cls < 2; cls++) {
-    if (!c->tl[cls][0].empty()) return 0;
+    if (!c->tl[cls][0].empty() || !c->tl[cls][3].empty()) return 0;   // (long-row tiles, regular or not)
     if (c->tl[cls][1].empty() && c->tl[cls][2].empty()) continue;
     const int qw = cls ? c->fast_qw2 : c->fast_qw, vl = cls ? c->fast_vl2 : c->fast_vl;
     if (!qw || !fast_supported(P.f, qw, vl)) return 0;
@@ -4024,12 +4083,23 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
     HIP_OK(c->r_n.ensure(32));
     HIP_OK(hipMemsetAsync(c->r_n.p, 0, 32, c->stream));
     int32_t* rn = c->r_n.as<int32_t>();   // [0] r1a, [1] r1b, [2] r2, [3] r3a, [4] r3b
+    if (!P.split2) {   // (split: the first pass's launches count with the second's)
+      c->reg_launched = 0;
+      c->reg_cls = 0;
+    }
+    const bool use_reg = !opt_off(OPT_REGULAR);   // 0: the regular lists through the ordinary kernel
     auto fast_launch = [&](int cls, int shortk, const int32_t* list, const int32_t* list_n, int64_t cap,
-                           int32_t* out, int32_t* out_n) -> int {
+                           int32_t* out, int32_t* out_n, bool reg = false) -> int {
       const int qw = cls ? c->fast_qw2 : c->fast_qw, vl = cls ? c->fast_vl2 : c->fast_vl;
       if (cap == 0 || !qw || !fast_supported(P.f, qw, vl)) return 1;   // not run: caller routes the list on
       GridParams fp = gp;
       fp.shortk = shortk;
+      fp.reg = c->reg.as<RegRow>();
+      fp.regular = reg ? 1 : 0;   // (a regular list: k_fast's REG form, the offsets computed from reg[])
+      if (reg) {
+        c->reg_launched += cap;
+        c->reg_cls |= 1 << cls;
+      }
       fp.unit_s = (qw == 2 && P.I % 1000 == 0 && P.B0 % 1000 == 0) ? 1 : 0;
       fp.In = (int32_t)(fp.unit_s ? P.I / 1000 : P.I);
       fp.B0n = fp.unit_s ? P.B0 / 1000 : P.B0;
@@ -4088,7 +4158,9 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
     }
     for (int cls = 0; cls < 2 && !none; cls++) {
       const int64_t n0 = (int64_t)c->tl[cls][0].size(), n1 = (int64_t)c->tl[cls][1].size();
-      const int64_t n2 = (int64_t)c->tl[cls][2].size();
+      const int64_t n2 = (int64_t)c->tl[cls][2].size(), n3 = (int64_t)c->tl[cls][3].size();
+      const int32_t* l3 = dl + c->tl_off[7 + cls];
+      const int32_t* dn3 = dn + 7 + cls;
       const int32_t* l0 = dl + c->tl_off[3 * cls];
       const int32_t* l1 = dl + c->tl_off[3 * cls + 1];
       const int32_t* l2 = dl + c->tl_off[3 * cls + 2];
@@ -4147,6 +4219,11 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
         if (rc < 0) return rc;
         if (rc == 1) { to_grid.push_back({l0, {dn0, n0}}); routed += n0; }
       }
+      if (n3) {   // the regular tiles: values only (option REGULAR 0: as the list above)
+        rc = fast_launch(cls, 0, l3, dn3, n3, c->r2.as<int32_t>(), rn + 2, use_reg);
+        if (rc < 0) return rc;
+        if (rc == 1) { to_grid.push_back({l3, {dn3, n3}}); routed += n3; }
+      }
     }
     to_grid.push_back({c->r2.as<int32_t>(), {rn + 2, nt}});
     if (!none && !c->tl_other.empty()) to_grid.push_back({dl + c->tl_off[6], {dn + 6, (int64_t)c->tl_other.size()}});
@@ -4187,8 +4264,12 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
 //   per row in the scan range: qualifier bytes + value bytes (incl. the meta byte)
 //                              + 4 B base time + 2 x 8 B CSR offsets;  per series: 4 B group id.
 // Cached per scan range (the batch is resident; the loop is O(rows)).
+// A row of a tile the last query launched through k_fast's REG form (a regular list, the
+// streaming path, option REGULAR not 0, not the NONE aggregator) is read without its qualifiers:
+// its 8-byte RegRow entry instead.
 void account(tsdbhip_ctx* c, const Plan& P) {
-  if (c->acct_valid && c->acct_ss == P.ss && c->acct_se == P.se && c->acct_none == P.none) {
+  const int reg = (c->fast_used && !P.none) ? c->reg_cls : 0;   // classes whose regular list ran through REG
+  if (c->acct_valid && c->acct_ss == P.ss && c->acct_se == P.se && c->acct_none == P.none && c->acct_reg == reg) {
     c->timing.datapoints = c->acct_dps;
     c->timing.bytes = c->acct_bytes;
     return;
@@ -4203,7 +4284,18 @@ void account(tsdbhip_ctx* c, const Plan& P) {
       bytes += (int64_t)c->h_qlen[r] + c->h_vlen[r] + 4 + 16;
     }
   }
+  if (reg) {
+    for (int cls = 0; cls < 2; cls++) {
+      if (!(reg & (1 << cls))) continue;   // (that class's list took another kernel: its qualifiers were read)
+      for (const int32_t t : c->tl[cls][3])
+        for (int64_t r = c->h_srp[c->tb[t]]; r < c->h_srp[c->te[t]]; r++) {
+          if ((int64_t)c->h_base[r] < P.ss || (int64_t)c->h_base[r] >= P.se) continue;
+          bytes += 8 - (int64_t)c->h_qlen[r];
+        }
+    }
+  }
   c->acct_valid = true;
+  c->acct_reg = reg;
   c->acct_none = P.none;
   c->acct_ss = P.ss;
   c->acct_se = P.se;
@@ -4680,7 +4772,7 @@ int sel_window(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
   if (!c->tl_other.empty()) return 0;
   int64_t nshort = 0;
   for (int cls = 0; cls < 2; cls++) {
-    if (!c->tl[cls][0].empty() || !c->tl[cls][2].empty()) return 0;
+    if (!c->tl[cls][0].empty() || !c->tl[cls][2].empty() || !c->tl[cls][3].empty()) return 0;
     nshort += (int64_t)c->tl[cls][1].size();
   }
   if (nshort == 0 || nshort != (int64_t)c->tb.size()) return 0;
@@ -4732,13 +4824,13 @@ int sel_window(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
       if (samp[t]) sl[cls].push_back(t);
   std::vector<int32_t> all(sl[0]);
   all.insert(all.end(), sl[1].begin(), sl[1].end());
-  const int32_t ncnt[7] = {0, (int32_t)sl[0].size(), 0, 0, (int32_t)sl[1].size(), 0, 0};
+  const int32_t ncnt[9] = {0, (int32_t)sl[0].size(), 0, 0, (int32_t)sl[1].size(), 0, 0, 0, 0};
   HIP_OK(c->samp_tl.ensure(std::max<size_t>(1, all.size()) * 4));
-  HIP_OK(c->samp_tl_n.ensure(8 * 4));
+  HIP_OK(c->samp_tl_n.ensure(9 * 4));
   HIP_OK(c->samp_tiles.ensure(std::max<size_t>(1, spos.size()) * 4));
   HIP_OK(c->samp_ptr.ensure((G + 1) * 4));
   if (!all.empty()) HIP_OK(hipMemcpyAsync(c->samp_tl.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipMemcpyAsync(c->samp_tl_n.p, ncnt, 7 * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipMemcpyAsync(c->samp_tl_n.p, ncnt, 9 * 4, hipMemcpyHostToDevice, c->stream));
   if (!spos.empty()) HIP_OK(hipMemcpyAsync(c->samp_tiles.p, spos.data(), spos.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIP_OK(hipMemcpyAsync(c->samp_ptr.p, sptr.data(), (G + 1) * 4, hipMemcpyHostToDevice, c->stream));
   // the sample pass's buffers (as sel_values)
@@ -4751,17 +4843,18 @@ int sel_window(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
   HIP_OK(hipMemsetAsync(c->sel_wr.p, 0, std::max<int64_t>(1, S), c->stream));
   HIP_OK(hipMemsetAsync(c->sel_uni.p, 0, std::max<int64_t>(1, G * K), c->stream));
   {
-    // run_device over the sampled tiles: the class lists swapped for the sample's
+    // run_device over the sampled tiles: the class lists swapped for the sample's (the regular
+    // lists are empty here: no long-row tiles)
     std::vector<int32_t> keep[2][3], keep_other;
-    int64_t keep_off[7];
+    int64_t keep_off[9];
     for (int cls = 0; cls < 2; cls++)
       for (int j = 0; j < 3; j++) keep[cls][j].swap(c->tl[cls][j]);
     keep_other.swap(c->tl_other);
     std::memcpy(keep_off, c->tl_off, sizeof(keep_off));
     c->tl[0][1] = sl[0];
     c->tl[1][1] = sl[1];
-    const int64_t off[7] = {0, 0, (int64_t)sl[0].size(), (int64_t)sl[0].size(), (int64_t)sl[0].size(),
-                            (int64_t)all.size(), (int64_t)all.size()};
+    const int64_t off[9] = {0, 0, (int64_t)sl[0].size(), (int64_t)sl[0].size(), (int64_t)sl[0].size(),
+                            (int64_t)all.size(), (int64_t)all.size(), (int64_t)all.size(), (int64_t)all.size()};
     std::memcpy(c->tl_off, off, sizeof(off));
     c->tl_dev_override = c->samp_tl.as<int32_t>();
     c->tln_dev_override = c->samp_tl_n.as<int32_t>();
@@ -5807,7 +5900,7 @@ int fused_pass(tsdbhip_ctx* c, const tsdbhip_query* qs, int n, Plan& P) {
   // K <= 64: k_short / k_rows / k_fast (KR 2); K > 64 (a day of 1m buckets): k_hwin's MULTI variant
   if (!hwin_slots(c, &q0, P, true) && (P.K > 64 || !fast_path_ok(c, &q0, P))) return 1;
   for (int cls = 0; cls < 2; cls++) {
-    if (c->tl[cls][0].empty() && c->tl[cls][1].empty() && c->tl[cls][2].empty()) continue;
+    if (c->tl[cls][0].empty() && c->tl[cls][1].empty() && c->tl[cls][2].empty() && c->tl[cls][3].empty()) continue;
     const int qw = cls ? c->fast_qw2 : c->fast_qw, vl = cls ? c->fast_vl2 : c->fast_vl;
     if (!qw || !fast_supported(P.f, qw, vl)) return 1;
   }
@@ -6977,6 +7070,8 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
     c->timing.group_reduce_ms = t02 - t01;  // cell sizing, scans and writes
     c->timing.total_ms = t02;
     c->timing.fast_ms = 0;
+    c->reg_launched = 0;   // (rollup generation has no REG form: every qualifier is read)
+    c->reg_cls = 0;
     account(c, P);
   }
   int64_t cells = 0;
@@ -7162,6 +7257,8 @@ extern "C" int tsdbhip_preagg_run(tsdbhip_ctx* c, const tsdbhip_preagg_spec* sp,
     c->timing.total_ms = t01 + t12;
     c->timing.fast_ms = 0;
     c->timing.fused_queries = 0;
+    c->reg_launched = 0;   // (accounted as the sum of full passes: today's bytes)
+    c->reg_cls = 0;
     account(c, Pacct);
   }
   int32_t err = tot->err;

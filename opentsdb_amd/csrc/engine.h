@@ -26,6 +26,14 @@ struct RowDesc {
 };
 static_assert(sizeof(RowDesc) == 48, "RowDesc layout");
 
+// Side array beside rows[]: a regular row -- 2-byte qualifiers only, not ROW_ERR / ROW_UNSORTED,
+// datapoint i at offset first + i * step seconds, step >= 1 (a one-point row: step 1).
+// step == 0: not regular.  Written by k_index with the row's flags, cleared by k_recede.
+struct RegRow {
+  uint32_t first, step;
+};
+static_assert(sizeof(RegRow) == 8, "RegRow layout");
+
 // RowDesc.flags
 enum : uint32_t {
   ROW_QW_MASK = 0x7,        // 2 = all 2-byte (second) qualifiers, 4 = all 4-byte (ms), 0 = mixed
@@ -251,6 +259,9 @@ struct GridParams {
   MultiPartials mp;
   int32_t dbg;           // k_short profiling switches (TSDBHIP_DBG, results invalid): 1 skip series end,
                          // 2 skip chunk fold, 8 consume loads, 16 stop after the descriptors, 32 load row 0 only
+  // k_fast REG: the launch's tiles hold regular rows only; their offsets come from reg[row]
+  const RegRow* reg;     // [n_rows] beside rows[]
+  int32_t regular;       // 1: launch k_fast's REG form (values only)
 };
 
 struct ReduceParams {
@@ -514,6 +525,8 @@ struct RegroupParams {
   int64_t* srp_new;           // [n_series + 1]
   RowDesc* rows_new;          // [n_rows]
   int32_t* gid_new;           // [n_series]
+  const RegRow* reg_old;      // [n_rows] the rows' RegRow entries: they move with their rows
+  RegRow* reg_new;            // [n_rows]
 };
 hipError_t regroup_scan(const RegroupParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_regroup(const RegroupParams& p, hipStream_t s);
@@ -532,6 +545,9 @@ struct AppendParams {
   int64_t* srp_new;           // [n_series + 1]
   RowDesc* rows_new;          // [n_rows]
   int32_t* gid_new;           // [n_series]
+  const RegRow* reg_old;      // [n_rows_old] the resident rows' RegRow entries, carried over
+  const RegRow* reg_delta;    // [n_delta] the delta rows' entries from their index pass
+  RegRow* reg_new;            // [n_rows]
 };
 hipError_t append_scan(const AppendParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_append(const AppendParams& p, hipStream_t s);
@@ -658,14 +674,17 @@ struct IndexClasses {
   uint32_t short_rows;    // rows k_index_short takes (one chunk, 2-byte qualifiers, 4-byte or 1-2-byte values)
   bool short_done;        // index_fused: k_index_short has run (classification included)
 };
-hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, const IndexBufs& b,
-                       int64_t n_rows, int32_t* err, IndexClasses* out, hipStream_t s);
+// reg: [n_rows] the rows' RegRow entries, written with their flags by whichever kernel indexes the row
+hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, RegRow* reg,
+                       const IndexBufs& b, int64_t n_rows, int32_t* err, IndexClasses* out, hipStream_t s);
 hipError_t index_classes(const uint8_t* qual, const RowDesc* rows, const IndexBufs& b, int64_t n_rows,
                          IndexClasses* out, hipStream_t s);
-hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, const IndexBufs& b,
-                      const IndexClasses& k, int64_t n_rows, int32_t* err, bool generic, hipStream_t s);
+hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, RegRow* reg,
+                      const IndexBufs& b, const IndexClasses& k, int64_t n_rows, int32_t* err, bool generic, hipStream_t s);
 // rows whose first datapoint is not after the series' earlier rows' datapoints: ROW_UNSORTED
-hipError_t index_recede(RowDesc* rows, const int64_t* srp, const uint8_t* qual, int64_t n_series, hipStream_t s);
+// (and no longer regular)
+hipError_t index_recede(RowDesc* rows, RegRow* reg, const int64_t* srp, const uint8_t* qual, int64_t n_series,
+                        hipStream_t s);
 hipError_t launch_grid(const GridParams& p, int ds_function_class, hipStream_t s);
 // k_fast: uniform float rows of one (qualifier width, value length) class; returns
 // hipErrorNotSupported when no specialisation exists for (f, qw, vl)

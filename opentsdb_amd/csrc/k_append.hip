@@ -62,6 +62,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_append(AppendParams p) {
     const int64_t j = r - p.srp_new[lo];
     const int64_t kept = append_kept(p.srp_old, e);
     uint4 v = j < kept ? src_old[(p.srp_old[e.x] + j) * 3 + part] : src_delta[((int64_t)e.z + (j - kept)) * 3 + part];
+    if (part == 0)   // the row's RegRow entry moves with it
+      p.reg_new[r] = j < kept ? p.reg_old[p.srp_old[e.x] + j] : p.reg_delta[(int64_t)e.z + (j - kept)];
     if (part == 2) v.x = (v.x & ~(uint32_t)ROW_SFIRST) | (j == 0 ? (uint32_t)ROW_SFIRST : 0u);
     dst[w] = v;
   }
@@ -119,7 +121,10 @@ __global__ __launch_bounds__(256) void k_recede_touched(AppendParams p, const in
         pos += w;
       }
     }
-    if (r >= first_delta && first <= M) p.rows_new[r].flags = d.flags | ROW_UNSORTED;
+    if (r >= first_delta && first <= M) {
+      p.rows_new[r].flags = d.flags | ROW_UNSORTED;
+      p.reg_new[r] = RegRow{0u, 0u};   // (an unsorted row is not regular)
+    }
     M = max(M, mx);
   }
 }

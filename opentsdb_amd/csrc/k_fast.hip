@@ -1,6 +1,6 @@
 // k_fast.hip -- instantiates the streaming kernel k_fast for ONE downsample function
 // (F_ID, set by the Makefile) and the four uniform row classes (qualifier width 2/4 x
-// value length 4/8).
+// value length 4/8), and its REG form (regular rows: values only) for 2-byte qualifiers.
 #include "kcommon.h"
 
 #ifndef F_ID
@@ -15,6 +15,12 @@
 #endif
 #ifndef SHORT6_VL4
 #define SHORT6_VL4 0   // 4: the float32 class takes 6 a lane too (measured no faster: profiles/r04ab)
+#endif
+#ifndef FAST_REG_D4
+#define FAST_REG_D4 4  // k_fast REG ring depth, 4-byte values (16 B a lane a slot)
+#endif
+#ifndef FAST_REG_D8
+#define FAST_REG_D8 3  // k_fast REG ring depth, 8-byte values (32 B a lane a slot)
 #endif
 #ifndef ROWS_D
 #define ROWS_D 2       // k_rows ring depth (a power of two: 64 rows per descriptor batch)
@@ -81,6 +87,20 @@ static hipError_t launch_fast_k(const GridParams& p, hipStream_t s) {
                        p.series_row_ptr, p.tile_begin, p.tile_end);
     return hipGetLastError();
   }
+  if constexpr (QW == 2 && (VL == 4 || VL == 8)) {
+    if (p.regular) {   // a regular tile list: values only, the offsets from GridParams.reg
+      // (KR 0 keeps its partials' addresses live: a fourth slot spilled VGPRs to scratch)
+      constexpr int DR = VL == 8 ? FAST_REG_D8 : KR == 0 ? 3 : FAST_REG_D4;
+      if (lds > 65536) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_fast<F, QW, VL, DR, KR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+      }
+      hipLaunchKernelGGL((k_fast<F, QW, VL, DR, KR, true>), dim3((unsigned)blocks), dim3(64 * p.waves), lds, s, p, p.rows,
+                         p.series_row_ptr, p.tile_begin, p.tile_end);
+      return hipGetLastError();
+    }
+  }
+  if (p.regular) return hipErrorNotSupported;
   if (lds > 65536) {
     hipError_t e = hipFuncSetAttribute((const void*)k_fast<F, QW, VL, D, KR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -44,12 +44,15 @@ static constexpr uint8_t HINT_SHORT = 0x80;   // hint bit: the row is k_index_sh
 
 struct IdxAcc {
   bool bad, allf, alli, vmax2, nan, negz, unsorted;
+  bool irr;            // some offset is not first + i * step (idx_regular)
+  int first, step;     // wave-uniform: the row's first offset and the second minus the first (ms)
   int lsb, lmin, lmax;
   double amax;
 };
 
 __device__ __forceinline__ void idx_acc_init(IdxAcc& a) {
   a.bad = false; a.allf = a.alli = a.vmax2 = true; a.nan = a.negz = a.unsorted = false;
+  a.irr = false; a.first = 0; a.step = 1000;
   a.lsb = INT32_MAX; a.lmin = 99; a.lmax = -1; a.amax = 0.0;
 }
 
@@ -62,8 +65,18 @@ __device__ __forceinline__ uint64_t stage_u64(const uint32_t* s, int b) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// the RegRow entry of a row of 2-byte qualifiers from its wave-uniform results (ms -> s)
+__device__ __forceinline__ RegRow reg_entry(bool regular, int first_ms, int step_ms) {
+  RegRow g;
+  const bool ok = regular && step_ms >= 1000;
+  g.first = ok ? (uint32_t)first_ms / 1000u : 0u;
+  g.step = ok ? (uint32_t)step_ms / 1000u : 0u;
+  return g;
+}
+
 __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual, const uint8_t* __restrict__ val,
-                                  uint8_t* __restrict__ val2, RowDesc* __restrict__ rows, int64_t r, int32_t* err) {
+                                  uint8_t* __restrict__ val2, RowDesc* __restrict__ rows, RegRow* __restrict__ reg,
+                                  int64_t r, int32_t* err) {
   const int lane = lane_id();
   {
     RowDesc d = rows[r];
@@ -131,6 +144,8 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
     long long vcarry = 0;
     uint32_t qcarry = 0;
     long long prev_off = -1;   // offset (ms) of the previous datapoint
+    bool irr = (flags & ROW_QW_MASK) != 2;   // regular (RegRow): 2-byte qualifiers at first + i * step
+    long long rfirst = 0, rstep = 1000;
     for (uint32_t i0 = 0; i0 < ndp; i0 += 64) {
       const uint32_t i = i0 + lane;
       const bool in = i < ndp;
@@ -169,6 +184,11 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
       long long po = __shfl_up(off, 1, 64);
       if (lane == 0) po = prev_off;
       if (in && off <= po) unsorted = true;
+      if (i0 == 0) {
+        rfirst = __shfl(off, 0, 64);
+        if (ndp > 1) rstep = __shfl(off, 1, 64) - rfirst;
+      }
+      if (in && off != rfirst + (long long)i * rstep) irr = true;
       prev_off = __shfl(off, (int)min((uint32_t)63, ndp - 1 - i0), 64);
       if (in && !fl) allf = false;
       if (in && fl) alli = false;
@@ -201,6 +221,7 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
     hasnan = __any(hasnan);
     negz = __any(negz);
     unsorted = __any(unsorted);
+    irr = __any(irr);
     lsbmin = wave_min(lsbmin);
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) amax = fmax(amax, __shfl_xor(amax, dd, 64));
@@ -222,6 +243,7 @@ __device__ __noinline__ void index_row_generic(const uint8_t* __restrict__ qual,
       d.lsb = lsbmin;
       d.absmax = amax;
       rows[r] = d;
+      reg[r] = reg_entry(!irr && !bad && !unsorted && ndp > 0, (int)rfirst, (int)rstep);
     }
   }
 }
@@ -413,6 +435,38 @@ __device__ __forceinline__ void idx_order(const int off[DPL], int nin, int64_t i
   prev_off = __shfl(last, (int)((min((int64_t)CH, (int64_t)w.ndp - i0) - 1) / DPL), 64);
 }
 
+// The row's regularity (RegRow): every offset first + i * step, with first and step from the
+// row's first two datapoints (lane 0 of chunk 0).  off in ms of 2-byte qualifiers.
+__device__ __forceinline__ void idx_regular(const int off[DPL], int nin, int64_t i0, const IdxRow& w, IdxAcc& a) {
+  if (i0 == 0) {
+    a.first = __builtin_amdgcn_readfirstlane(off[0]);
+    a.step = w.ndp > 1 ? __builtin_amdgcn_readfirstlane(off[1]) - a.first : 1000;
+  }
+  int e = a.first + ((int)i0 + lane_id() * DPL) * a.step;
+  bool irr = false;
+#pragma unroll
+  for (int j = 0; j < DPL; j++) {
+    irr |= (j < nin) & (off[j] != e);
+    e += a.step;
+  }
+  a.irr |= irr;
+}
+
+// Order and regularity of a chunk.  A row regular so far, with step >= 1, is strictly increasing
+// up to this chunk's end: the order test runs only for the others (wave-uniform branch), so a
+// regular row pays the regularity compare instead of the order compare, not both.
+template <int QW>
+__device__ __forceinline__ void idx_order_regular(const int off[DPL], int nin, int64_t i0, const IdxRow& w, int& prev_off,
+                                                  IdxAcc& a) {
+  if (QW != 2) { idx_order(off, nin, i0, w, prev_off, a); return; }
+  idx_regular(off, nin, i0, w, a);
+  if (__any(a.irr) || a.step < 1000) {
+    idx_order(off, nin, i0, w, prev_off, a);
+  } else {   // the chunk's last offset, as idx_order leaves it
+    prev_off = a.first + (int)(i0 + min((int64_t)CH, (int64_t)w.ndp - i0) - 1) * a.step;
+  }
+}
+
 // int16 copy of the lane's 8 values (1-2-byte integers; other lanes' slots are never read:
 // val2 is consulted only for rows whose every value is a 1-2-byte integer)
 __device__ __forceinline__ void idx_val2(uint8_t* __restrict__ val2, const IdxRow& w, int64_t i, const int len[DPL],
@@ -502,7 +556,7 @@ __device__ __forceinline__ bool idx_chunk_var(const uint8_t* __restrict__ val, u
   a.bad |= bad;
   a.lmin = min(a.lmin, lmin);
   a.lmax = max(a.lmax, lmax);
-  idx_order(off, nin, i0, w, prev_off, a);
+  idx_order_regular<QW>(off, nin, i0, w, prev_off, a);
   // stage the chunk's value bytes
   const uint8_t* v = val + w.voff;
   const int incl = wave_incl_sum_dpp(lsum);
@@ -579,7 +633,7 @@ __device__ __forceinline__ bool idx_chunk_uni(uint8_t* __restrict__ val2, const 
   a.allf &= fl_and != 0;
   a.alli &= fl_or == 0;
   if (L <= 2) a.bad |= fl_or != 0;   // a float of 1 or 2 bytes
-  idx_order(off, nin, i0, w, prev_off, a);
+  idx_order_regular<QW>(off, nin, i0, w, prev_off, a);
   const uint32_t* vw = &ld.v[0].x;
   int len[DPL];
 #pragma unroll
@@ -655,6 +709,7 @@ __device__ __forceinline__ bool idx_chunk_uni(uint8_t* __restrict__ val2, const 
 template <int QW, int L, bool V2>
 __global__ __launch_bounds__(256) void k_index_cls(const uint8_t* __restrict__ qual, const uint8_t* __restrict__ val,
                                                    uint8_t* __restrict__ val2, RowDesc* __restrict__ rows,
+                                                   RegRow* __restrict__ reg,
                                                    uint8_t* __restrict__ hint, const int32_t* __restrict__ list,
                                                    int64_t n, int32_t* err) {
   __shared__ uint32_t stage_all[4][L == 0 ? IDX_STAGE / 4 : 1];
@@ -694,6 +749,7 @@ __global__ __launch_bounds__(256) void k_index_cls(const uint8_t* __restrict__ q
       const bool allf = __all(a.allf), alli = __all(a.alli);
       const bool vmax2 = L != 0 ? L <= 2 : __all(a.vmax2);
       const bool hasnan = __any(a.nan), negz = __any(a.negz), unsorted = __any(a.unsorted);
+      const bool regular = QW == 2 && cur.ndp > 0 && !bad && !unsorted && !__any(a.irr);
       const int lsbmin = wave_min(a.lsb);
       const int lmin = L != 0 ? L : wave_min(a.lmin), lmax = L != 0 ? L : wave_max(a.lmax);
       double amax = a.amax;
@@ -719,6 +775,7 @@ __global__ __launch_bounds__(256) void k_index_cls(const uint8_t* __restrict__ q
         o.flags = flags;
         o.lsb = lsbmin;
         o.absmax = amax;
+        reg[cur.r] = reg_entry(regular, a.first, a.step);
       }
     }
     if (!has_next) break;
@@ -766,7 +823,23 @@ struct ShortRes {
   int32_t lsb;
   double amax;
   bool fail;
+  uint32_t first, step;   // the row's RegRow entry (step 0: not regular)
 };
+
+// Offsets (seconds) of the lane's datapoints against first + i * step, first and step from lane
+// 0's first two; false in some lane = not regular.  Every lane calls it.
+__device__ __forceinline__ bool short_regular(const uint32_t o[DPL], int nin, uint32_t cn, uint32_t& first, int& step) {
+  first = (uint32_t)__builtin_amdgcn_readfirstlane((int)o[0]);
+  step = cn > 1 ? __builtin_amdgcn_readfirstlane((int)o[1]) - (int)first : 1;
+  int e = (int)first + lane_id() * DPL * step;
+  bool irr = false;
+#pragma unroll
+  for (int k = 0; k < DPL; k++) {
+    irr |= (k < nin) & ((int)o[k] != e);
+    e += step;
+  }
+  return !irr;
+}
 
 __device__ __forceinline__ ShortRes short_row_general(const ShortLd& ld, uint8_t* __restrict__ val2, const uint8_t* st8,
                                                       uint4* stage, uint64_t cq, uint32_t cn, uint32_t cvl, bool cu4) {
@@ -896,6 +969,16 @@ __device__ __forceinline__ ShortRes short_row_general(const ShortLd& ld, uint8_t
   if (__any(negz)) flags |= ROW_NEGZ;
   if (__any(uns)) flags |= ROW_UNSORTED;
   R.flags = flags;   // (ROW_NOCERT: k_index_short, per lane at the batch end)
+  {
+    uint32_t o[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) o[k] = qq[k] >> 4;
+    int step;
+    const bool rg = short_regular(o, nin, cn, R.first, step);
+    const bool ok = __all(rg) && step >= 1 && cn > 0 && !R.fail && !(flags & (ROW_ERR | ROW_UNSORTED));
+    R.step = ok ? (uint32_t)step : 0u;
+    R.first = ok ? R.first : 0u;
+  }
   return R;
 }
 
@@ -905,7 +988,30 @@ __device__ __forceinline__ ShortRes short_row_general(const ShortLd& ld, uint8_t
 // and value bit patterns; false = a premise fails (a flag nibble off the class, offsets not
 // strictly increasing or a 4-byte qualifier, NaN, a denormal, values past the row, ...) and
 // short_row_general decodes the row -- whose results these equal wherever they return true.
-__device__ __forceinline__ bool short_full_order(const uint32_t t[4], bool act) {
+// rg: the row is regular, first + i * step with step >= 1 (a full-lane row has >= 8 points)
+__device__ __forceinline__ bool short_full_order(const uint32_t t[4], bool act, bool& rg, uint32_t& first, int& step) {
+  // The regular row first, on the packed words (two qualifiers a word, offsets in bits 20-31 and
+  // 4-15): first and step from lane 0's first word; every word against its expected offsets.  A
+  // lane whose last expected offset reaches 0xF00 fails (the fields would carry, and such a
+  // qualifier reads as a 4-byte one), so a match is exact; it implies strictly increasing
+  // offsets below 0xF00, the whole of the order test below.  rg is wave-uniform.
+  const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)t[0]);
+  first = t0 >> 20;
+  step = (int)((t0 >> 4) & 0xFFFu) - (int)first;
+  rg = false;
+  if (step >= 1) {
+    const uint32_t e0 = first + (uint32_t)(lane_id() * DPL) * (uint32_t)step;
+    const uint32_t D = ((uint32_t)(2 * step) << 20) | ((uint32_t)(2 * step) << 4);
+    uint32_t E = (e0 << 20) | ((e0 + (uint32_t)step) << 4);
+    bool irr = e0 + (uint32_t)(DPL - 1) * (uint32_t)step >= 0xF00u;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      irr |= (t[i] & 0xFFF0FFF0u) != E;
+      E += D;
+    }
+    rg = __all(!act || !irr);
+  }
+  if (rg) return true;
   uint32_t o[DPL];
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -925,8 +1031,12 @@ __device__ __forceinline__ bool short_full_u4(const ShortLd& ld, bool act, Short
                          __builtin_bswap32(ld.q.w)};
   // float32 of 4 bytes everywhere: flag nibble 0xB
   const uint32_t fx = ((t[0] ^ 0x000B000Bu) | (t[1] ^ 0x000B000Bu) | (t[2] ^ 0x000B000Bu) | (t[3] ^ 0x000B000Bu)) & 0x000F000Fu;
-  const bool ord = short_full_order(t, act);   // (every lane: a DPP step inside)
+  bool rg;
+  int step;
+  const bool ord = short_full_order(t, act, rg, R.first, step);   // (every lane: a DPP step inside)
   if (!__all(!act || (fx == 0 && ord))) return false;
+  R.step = (__all(rg) && step >= 1) ? (uint32_t)step : 0u;   // (sorted: every premise above holds)
+  if (!R.step) R.first = 0;
   const uint32_t vw[8] = {ld.v0.x, ld.v0.y, ld.v0.z, ld.v0.w, ld.v1.x, ld.v1.y, ld.v1.z, ld.v1.w};
   uint32_t amax = 0, lsbk = 0xFFFFFFFFu;
   bool odd = false;
@@ -960,8 +1070,12 @@ __device__ __forceinline__ bool short_full_vle(const ShortLd& ld, uint8_t* __res
                          __builtin_bswap32(ld.q.w)};
   // integers of 1 or 2 bytes everywhere: flag nibble 0 or 1
   const uint32_t fx = (t[0] | t[1] | t[2] | t[3]) & 0x000E000Eu;
-  const bool ord = short_full_order(t, act);   // (every lane: a DPP step inside)
+  bool rg;
+  int step;
+  const bool ord = short_full_order(t, act, rg, R.first, step);   // (every lane: a DPP step inside)
   if (!__all(!act || (fx == 0 && ord))) return false;
+  R.step = (__all(rg) && step >= 1) ? (uint32_t)step : 0u;
+  if (!R.step) R.first = 0;
   // 2-byte values: bit k of lb (datapoint k of the lane)
   uint32_t lb = 0;
 #pragma unroll
@@ -1033,6 +1147,7 @@ __device__ __forceinline__ ShortRes short_row(const ShortLd& ld, uint8_t* __rest
 template <int SD, bool CLS>
 __global__ __launch_bounds__(256) void k_index_short(const uint8_t* __restrict__ qual, const uint8_t* __restrict__ val,
                                                      uint8_t* __restrict__ val2, RowDesc* __restrict__ rows,
+                                                     RegRow* __restrict__ reg,
                                                      uint8_t* __restrict__ hint, int64_t n_rows, uint32_t* cnt,
                                                      int32_t* err) {
   uint32_t* fails = cnt + IDX_C_FAIL;
@@ -1091,7 +1206,7 @@ __global__ __launch_bounds__(256) void k_index_short(const uint8_t* __restrict__
     if (CLS && !todo) continue;
     if (!mine) qlen = 0;
     const uint32_t u4m = (uint32_t)((h & 0x7F) == idx_cls(2, 4));
-    uint32_t o_flags = 0, o_alo = 0, o_ahi = 0;
+    uint32_t o_flags = 0, o_alo = 0, o_ahi = 0, o_first = 0, o_step = 0;
     int32_t o_lsb = INT32_MAX;
     auto issue = [&](int jj, ShortLd& ld) {
       const uint64_t qo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(qoff >> 32), jj) << 32) |
@@ -1121,6 +1236,8 @@ __global__ __launch_bounds__(256) void k_index_short(const uint8_t* __restrict__
           o_lsb = me ? R.lsb : o_lsb;
           o_alo = me ? (uint32_t)ab : o_alo;
           o_ahi = me ? (uint32_t)(ab >> 32) : o_ahi;
+          o_first = me ? R.first : o_first;
+          o_step = me ? R.step : o_step;
         }
         issue(min(j + SD, 63), buf[i]);
       }
@@ -1137,6 +1254,9 @@ __global__ __launch_bounds__(256) void k_index_short(const uint8_t* __restrict__
         o.flags = (o_flags | (fin & ROW_SFIRST)) | (row_nocert(o_lsb, amax) ? ROW_NOCERT : 0u);
         o.lsb = o_lsb;
         o.absmax = amax;
+        RegRow g;
+        g.first = o_first; g.step = o_step;
+        reg[r] = g;
         if (o_flags & ROW_ERR) set_err(err, TSDB_E_ILLEGAL_DATA);
       }
     }
@@ -1147,6 +1267,7 @@ __global__ __launch_bounds__(256) void k_index_short(const uint8_t* __restrict__
 // A wave scans 64 hints at a time and walks the rows its ballot selects.
 __global__ __launch_bounds__(256) void k_index_generic(const uint8_t* __restrict__ qual, const uint8_t* __restrict__ val,
                                                        uint8_t* __restrict__ val2, RowDesc* __restrict__ rows,
+                                                       RegRow* __restrict__ reg,
                                                        const uint8_t* __restrict__ hint, int64_t n_rows, int32_t* err,
                                                        int all, const uint32_t* need) {
   // need (non-null): the count of rows handed back by k_index_short -- the only rows left to
@@ -1160,22 +1281,22 @@ __global__ __launch_bounds__(256) void k_index_generic(const uint8_t* __restrict
     while (m) {
       const int l = __ffsll((long long)m) - 1;
       m &= m - 1;
-      index_row_generic(qual, val, val2, rows, r0 + l, err);
+      index_row_generic(qual, val, val2, rows, reg, r0 + l, err);
     }
   }
 }
 
 template <int QW, int L>
-static hipError_t launch_cls(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, const IndexBufs& b,
+static hipError_t launch_cls(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, RegRow* reg, const IndexBufs& b,
                              const uint32_t* off, const uint32_t* cnt, int32_t* err, hipStream_t s) {
   const int c = idx_cls(QW, L);
   if (!cnt[c]) return hipSuccess;
   const int64_t blocks = std::min<int64_t>(((int64_t)cnt[c] + 3) / 4, 8192);
   if (QW == 2 && L <= 2 && val2)
-    hipLaunchKernelGGL((k_index_cls<QW, L, true>), dim3((unsigned)blocks), dim3(256), 0, s, qual, val, val2, rows,
+    hipLaunchKernelGGL((k_index_cls<QW, L, true>), dim3((unsigned)blocks), dim3(256), 0, s, qual, val, val2, rows, reg,
                        b.hint, b.list + off[c], (int64_t)cnt[c], err);
   else
-    hipLaunchKernelGGL((k_index_cls<QW, L, false>), dim3((unsigned)blocks), dim3(256), 0, s, qual, val, val2, rows,
+    hipLaunchKernelGGL((k_index_cls<QW, L, false>), dim3((unsigned)blocks), dim3(256), 0, s, qual, val, val2, rows, reg,
                        b.hint, b.list + off[c], (int64_t)cnt[c], err);
   return hipGetLastError();
 }
@@ -1213,7 +1334,7 @@ hipError_t index_classes(const uint8_t* qual, const RowDesc* rows, const IndexBu
 // index_classes + k_index_short in one pass over the batch (val2 allocated up front): the short
 // rows indexed while the rest are classified; then, only if some row is not short, the class
 // row lists.  index_rows runs the rest (class kernels, k_index_generic).
-hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, const IndexBufs& b,
+hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, RegRow* reg, const IndexBufs& b,
                        int64_t n_rows, int32_t* err, IndexClasses* out, hipStream_t s) {
   *out = IndexClasses{};
   if (n_rows == 0) return hipSuccess;
@@ -1222,7 +1343,7 @@ hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, R
   if ((e = hipMemsetAsync(b.cnt, 0, 16 * 4, s)) != hipSuccess) return e;
   const int64_t tiles = (n_rows + 63) / 64;
   hipLaunchKernelGGL((k_index_short<IDX_SHORT_D, true>), dim3((unsigned)std::min<int64_t>((tiles + 3) / 4, IDX_SHORT_BLOCKS)),
-                     dim3(256), 0, s, qual, val, val2, rows, b.hint, n_rows, b.cnt, err);
+                     dim3(256), 0, s, qual, val, val2, rows, reg, b.hint, n_rows, b.cnt, err);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   uint32_t cnt[16] = {}, cur[16] = {};
   if ((e = hipMemcpyAsync(cnt, b.cnt, 16 * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
@@ -1244,12 +1365,12 @@ hipError_t index_fused(const uint8_t* qual, const uint8_t* val, uint8_t* val2, R
   return hipGetLastError();
 }
 
-hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, const IndexBufs& b,
+hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, RowDesc* rows, RegRow* reg, const IndexBufs& b,
                       const IndexClasses& k, int64_t n_rows, int32_t* err, bool generic, hipStream_t s) {
   if (n_rows == 0) return hipSuccess;
   const int64_t gblocks = std::min<int64_t>((n_rows + 3) / 4, 16384);
   if (generic) {
-    hipLaunchKernelGGL(k_index_generic, dim3((unsigned)gblocks), dim3(256), 0, s, qual, val, val2, rows, b.hint, n_rows,
+    hipLaunchKernelGGL(k_index_generic, dim3((unsigned)gblocks), dim3(256), 0, s, qual, val, val2, rows, reg, b.hint, n_rows,
                        err, 1, nullptr);
     return hipGetLastError();
   }
@@ -1257,10 +1378,10 @@ hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, Ro
   if (k.short_rows && !k.short_done) {
     const int64_t tiles = (n_rows + 63) / 64;
     hipLaunchKernelGGL((k_index_short<IDX_SHORT_D, false>), dim3((unsigned)std::min<int64_t>((tiles + 3) / 4, IDX_SHORT_BLOCKS)),
-                       dim3(256), 0, s, qual, val, val2, rows, b.hint, n_rows, b.cnt, err);
+                       dim3(256), 0, s, qual, val, val2, rows, reg, b.hint, n_rows, b.cnt, err);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-#define IDX_CLS(Q, LL) if ((e = launch_cls<Q, LL>(qual, val, val2, rows, b, k.off, k.cnt, err, s)) != hipSuccess) return e;
+#define IDX_CLS(Q, LL) if ((e = launch_cls<Q, LL>(qual, val, val2, rows, reg, b, k.off, k.cnt, err, s)) != hipSuccess) return e;
   IDX_CLS(2, 0) IDX_CLS(2, 1) IDX_CLS(2, 2) IDX_CLS(2, 4) IDX_CLS(2, 8)
   IDX_CLS(4, 0) IDX_CLS(4, 1) IDX_CLS(4, 2) IDX_CLS(4, 4) IDX_CLS(4, 8)
 #undef IDX_CLS
@@ -1268,7 +1389,7 @@ hipError_t index_rows(const uint8_t* qual, const uint8_t* val, uint8_t* val2, Ro
   // k_index_short ran (its hand-back counter); otherwise the kernel scans every hint
   const bool early_out = k.cnt[0] == 0 && k.listed == 0;
   hipLaunchKernelGGL(k_index_generic, dim3((unsigned)std::min<int64_t>(gblocks, 4096)), dim3(256), 0, s, qual, val,
-                     nullptr, rows, b.hint, n_rows, err, 0, early_out ? b.cnt + IDX_C_FAIL : nullptr);
+                     nullptr, rows, reg, b.hint, n_rows, err, 0, early_out ? b.cnt + IDX_C_FAIL : nullptr);
   return hipGetLastError();
 }
 
@@ -1288,7 +1409,8 @@ __device__ __forceinline__ int64_t qual_ms_at(const uint8_t* q, uint32_t pos, in
   return (int64_t)(((((uint32_t)q[pos] << 8) | q[pos + 1]) >> 4) & 0xFFF) * 1000;
 }
 
-__global__ __launch_bounds__(256) void k_recede(RowDesc* __restrict__ rows, const int64_t* __restrict__ srp,
+__global__ __launch_bounds__(256) void k_recede(RowDesc* __restrict__ rows, RegRow* __restrict__ reg,
+                                                const int64_t* __restrict__ srp,
                                                 const uint8_t* __restrict__ qual, int64_t n_series) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_series) return;
@@ -1313,14 +1435,18 @@ __global__ __launch_bounds__(256) void k_recede(RowDesc* __restrict__ rows, cons
         pos += w;
       }
     }
-    if (first <= M) rows[r].flags = d.flags | ROW_UNSORTED;
+    if (first <= M) {
+      rows[r].flags = d.flags | ROW_UNSORTED;
+      reg[r] = RegRow{0u, 0u};   // (an unsorted row is not regular)
+    }
     M = max(M, mx);
   }
 }
 
-hipError_t index_recede(RowDesc* rows, const int64_t* srp, const uint8_t* qual, int64_t n_series, hipStream_t s) {
+hipError_t index_recede(RowDesc* rows, RegRow* reg, const int64_t* srp, const uint8_t* qual, int64_t n_series,
+                        hipStream_t s) {
   if (n_series <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_recede, dim3((unsigned)((n_series + 255) / 256)), dim3(256), 0, s, rows, srp, qual, n_series);
+  hipLaunchKernelGGL(k_recede, dim3((unsigned)((n_series + 255) / 256)), dim3(256), 0, s, rows, reg, srp, qual, n_series);
   return hipGetLastError();
 }
 

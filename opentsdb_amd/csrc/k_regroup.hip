@@ -48,6 +48,7 @@ __global__ __launch_bounds__(REGROUP_BLOCK) void k_regroup(RegroupParams p) {
     }
     const int64_t sr = p.srp_old[p.ent[lo].x] + (r - p.srp_new[lo]);
     dst[w] = src[sr * 3 + part];
+    if (part == 0) p.reg_new[r] = p.reg_old[sr];   // the row's RegRow entry moves with it
   }
 }
 

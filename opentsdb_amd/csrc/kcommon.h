@@ -1595,14 +1595,23 @@ struct FMeta {
   int32_t rrel;    // row index relative to the tile's first row
 };
 enum : uint32_t { FM_NV = 0x1FFFFFFFu, FM_OK = 1u << 29, FM_NEWSER = 1u << 30, FM_NEWROW = 1u << 31 };
+// REG (regular rows, RegRow): the chunk's offsets are f0 + i * step, computed and not loaded
+struct FMetaReg : FMeta {
+  uint32_t f0;     // offset field of the chunk's first datapoint: first + c0 * step
+  uint32_t step;
+};
 
 // VL == 0: the vle-integer class (values of 1 or 2 bytes, rows of <= CH datapoints): the
 // lane loads a fixed 16-byte slice of the row's value bytes; values are located after a
 // wave prefix sum of the qualifier lengths and read back from an LDS stage.
-template <int QW, int VL>
+template <int QW, int VL, bool REG = false>
 struct FRaw {
   uint4 q[QW / 2];               // 8 qualifiers of QW bytes
   uint4 v[VL == 0 ? 1 : VL / 2]; // 8 values of VL bytes / a 16-B slice of the row's values
+};
+template <int QW, int VL>
+struct FRaw<QW, VL, true> {      // REG: values only
+  uint4 v[VL / 2];
 };
 
 template <int F>
@@ -1683,12 +1692,24 @@ __device__ __forceinline__ bool fast_row_ok(uint32_t flags, bool minmax, bool ce
 struct FDesc {       // the descriptor fields the walker needs
   uint64_t qoff, voff;
   uint32_t base, ndp, flags;
+  uint32_t first, step;   // REG: the row's RegRow entry
 };
 
 __device__ __forceinline__ FDesc fdesc(const RowDesc* __restrict__ rows, int64_t r) {
   const RowDesc& x = rows[r];
   FDesc d;
   d.qoff = x.qoff; d.voff = x.voff; d.base = x.base; d.ndp = x.ndp; d.flags = x.flags;
+  d.first = d.step = 0;
+  return d;
+}
+
+template <bool REG>
+__device__ __forceinline__ FDesc fdesc_r(const GridParams& p, const RowDesc* __restrict__ rows, int64_t r) {
+  FDesc d = fdesc(rows, r);
+  if constexpr (REG) {
+    const RegRow g = p.reg[r];
+    d.first = g.first; d.step = g.step;
+  }
   return d;
 }
 
@@ -1700,28 +1721,30 @@ struct FWalk {
   FDesc d, nd;       // rows r and r + 1
 };
 
-__device__ __forceinline__ void fwalk_next_row(const RowDesc* __restrict__ rows, FWalk& w) {
+template <bool REG = false>
+__device__ __forceinline__ void fwalk_next_row(const GridParams& p, const RowDesc* __restrict__ rows, FWalk& w) {
   w.r++;
   w.c0 = 0;
   w.d = w.nd;
-  if (w.r + 1 < w.rend) w.nd = fdesc(rows, w.r0 + w.r + 1);
+  if (w.r + 1 < w.rend) w.nd = fdesc_r<REG>(p, rows, w.r0 + w.r + 1);
 }
 
 // 0 = chunk issued, 1 = end of tile, 2 = row the kernel cannot take (redo the tile)
-template <int F, int QW, int VL>
+template <int F, int QW, int VL, bool REG = false, class M = FMeta>
 __device__ __forceinline__ int fast_issue(const GridParams& p, const RowDesc* __restrict__ rows, FWalk& w,
-                                          FRaw<QW, VL>& b, FMeta& m) {
+                                          FRaw<QW, VL, REG>& b, M& m) {
   m.bits = 0;
   for (;;) {
     if (w.r >= w.rend) return 1;
     if (w.c0 == 0) {
       w.sf |= (w.d.flags & ROW_SFIRST) != 0;
-      if ((int64_t)w.d.base < p.ss || (int64_t)w.d.base >= p.se) { fwalk_next_row(rows, w); continue; }
+      if ((int64_t)w.d.base < p.ss || (int64_t)w.d.base >= p.se) { fwalk_next_row<REG>(p, rows, w); continue; }
       if (!fast_row_ok<QW, VL>(w.d.flags, F == F_MIN || F == F_MAX, F == F_SUM || F == F_AVG)) return 2;
       if (VL == 0 && w.d.ndp > CH) return 2;
+      if (REG && w.d.step == 0) return 2;   // (not on a correct regular list)
     }
     if (w.c0 < (int64_t)w.d.ndp) break;
-    fwalk_next_row(rows, w);
+    fwalk_next_row<REG>(p, rows, w);
   }
   const int lane = lane_id();
   const int nv0 = (int)w.d.ndp - w.c0;
@@ -1730,11 +1753,16 @@ __device__ __forceinline__ int fast_issue(const GridParams& p, const RowDesc* __
   w.sf = 0;
   // lanes past the end of the row re-read its first datapoints (in bounds, ignored)
   const int64_t i0 = (lane * DPL < nv0) ? w.c0 + (int64_t)lane * DPL : 0;
-  const uint4* q = reinterpret_cast<const uint4*>(p.qual + w.d.qoff + i0 * QW);
+  if constexpr (REG) {
+    m.f0 = w.d.first + (uint32_t)w.c0 * w.d.step;
+    m.step = w.d.step;
+  } else {
+    const uint4* q = reinterpret_cast<const uint4*>(p.qual + w.d.qoff + i0 * QW);
 #pragma unroll
-  for (int k = 0; k < QW / 2; k++) b.q[k] = q[k];
+    for (int k = 0; k < QW / 2; k++) b.q[k] = q[k];
+  }
   if (VL == 0) {
-    b.v[0] = *reinterpret_cast<const uint4*>(p.val2 + w.d.qoff + i0 * 2);   // the lane's 8 int16 values
+    if constexpr (!REG) b.v[0] = *reinterpret_cast<const uint4*>(p.val2 + w.d.qoff + i0 * 2);   // the lane's 8 int16 values
   } else {
     const uint4* v = reinterpret_cast<const uint4*>(p.val + w.d.voff + i0 * VL);
 #pragma unroll
@@ -1758,8 +1786,8 @@ __device__ __forceinline__ uint32_t f_field(const FRaw<QW, VL>& b, int j) {
   }
 }
 
-template <int QW, int VL>
-__device__ __forceinline__ double f_value(const FRaw<QW, VL>& b, int j) {
+template <int QW, int VL, bool REG = false>
+__device__ __forceinline__ double f_value(const FRaw<QW, VL, REG>& b, int j) {
   if (VL == 4) {
     const uint4 u = b.v[j >> 2];
     const uint32_t wd = (j & 3) == 0 ? u.x : (j & 3) == 1 ? u.y : (j & 3) == 2 ? u.z : u.w;
@@ -1790,8 +1818,8 @@ __device__ __forceinline__ uint32_t f_flags(const FRaw<QW, VL>& b, int j) {
 // src/core/RowSeq.java:233-245), read from the load-time int16 copy of the row's values
 // (k_index writes val2[qoff + 2 i] for every 1-2-byte integer of a 2-byte-qualifier row), so
 // the query needs no in-wave prefix sum of value lengths and no LDS staging.
-template <int QW, int VL>
-__device__ __forceinline__ int f_int16(const FRaw<QW, VL>& b, int j) {
+template <int QW, int VL, bool REG = false>
+__device__ __forceinline__ int f_int16(const FRaw<QW, VL, REG>& b, int j) {
   const uint32_t wd = (j >> 1) == 0 ? b.v[0].x : (j >> 1) == 1 ? b.v[0].y : (j >> 1) == 2 ? b.v[0].z : b.v[0].w;
   return (j & 1) ? ((int)wd >> 16) : (int)(int16_t)(wd & 0xFFFF);
 }
@@ -1802,8 +1830,8 @@ __device__ __forceinline__ void f_values_vle(const FastLds& L, const FRaw<QW, VL
   for (int j = 0; j < DPL; j++) xs[j] = (double)f_int16<QW, VL>(b, j);
 }
 
-template <int QW, int VL, int NP = DPL>
-__device__ __forceinline__ void f_values_vle_i(const FastLds& L, const FRaw<QW, VL>& b, int nvl, int xi[NP]) {
+template <int QW, int VL, int NP = DPL, bool REG = false>
+__device__ __forceinline__ void f_values_vle_i(const FastLds& L, const FRaw<QW, VL, REG>& b, int nvl, int xi[NP]) {
 #pragma unroll
   for (int j = 0; j < NP; j++) xi[j] = f_int16<QW, VL>(b, j);
 }
@@ -1830,15 +1858,22 @@ __device__ __forceinline__ int f_slot(const GridParams& p, const FGeom& m, int n
 }
 
 // Folds one chunk into the series' slot accumulators.
-template <int F, int QW, int VL, bool FULL, int NP = DPL>
-__device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L, const FRaw<QW, VL>& b,
-                                           const FGeom& m, int nv0, int K) {
+// REG: the offset fields are f0 + i * step (i: the datapoint's place in the chunk)
+template <int F, int QW, int VL, bool FULL, int NP = DPL, bool REG = false>
+__device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L, const FRaw<QW, VL, REG>& b,
+                                           const FGeom& m, int nv0, int K, uint32_t f0 = 0, uint32_t step = 0) {
   const int lane = lane_id();
   const int nvl = FULL ? NP : max(0, min(NP, nv0 - lane * NP));
   const int uq = (QW == 2 && !p.unit_s) ? 1000 : 1;
   uint32_t fld[NP];
+  if constexpr (REG) {
+    const uint32_t fl0 = f0 + (uint32_t)(lane * NP) * step;
 #pragma unroll
-  for (int j = 0; j < NP; j++) fld[j] = f_field<QW, VL>(b, j);
+    for (int j = 0; j < NP; j++) fld[j] = fl0 + (uint32_t)j * step;
+  } else {
+#pragma unroll
+    for (int j = 0; j < NP; j++) fld[j] = f_field<QW, VL>(b, j);
+  }
   // vle integers (1-2 bytes): the in-lane runs are folded in int32 (8 values of |x| < 2^15
   // sum exactly) and converted once per run; squareSum stays in double
   constexpr bool IP = (VL == 0) && (F != F_SQUARESUM);
@@ -1944,19 +1979,25 @@ __device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L
 // reduction and one fold.  A fold a lane would serialise ~45 LDS atomics on one slot.  Any
 // association is exact here (the series' certificate covers every partial sum), min / max are
 // order-free.  Called by the whole wave; false = not one bucket (nothing folded).
-template <int F, int QW, int VL, int NP = DPL>
-__device__ __forceinline__ bool fast_chunk_oneb(const GridParams& p, const FastLds& L, const FRaw<QW, VL>& b,
-                                                const FGeom& m, int nv0, int K) {
+template <int F, int QW, int VL, int NP = DPL, bool REG = false>
+__device__ __forceinline__ bool fast_chunk_oneb(const GridParams& p, const FastLds& L, const FRaw<QW, VL, REG>& b,
+                                                const FGeom& m, int nv0, int K, uint32_t f0 = 0, uint32_t step = 0) {
   const int lane = lane_id();
   const int n = min(nv0, 64 * NP);
   const int nvl = max(0, min(NP, n - lane * NP));
   const int uq = (QW == 2 && !p.unit_s) ? 1000 : 1;
-  const int ll = (n - 1) / NP, jl = (n - 1) % NP;   // the chunk's last datapoint: lane, slot
-  uint32_t fl = 0;
+  int n0, nl;
+  if constexpr (REG) {
+    n0 = m.r0 + (int)f0 * uq;
+    nl = m.r0 + (int)(f0 + (uint32_t)(n - 1) * step) * uq;
+  } else {
+    const int ll = (n - 1) / NP, jl = (n - 1) % NP;   // the chunk's last datapoint: lane, slot
+    uint32_t fl = 0;
 #pragma unroll
-  for (int j = 0; j < NP; j++) if (j == jl) fl = f_field<QW, VL>(b, j);
-  const int n0 = m.r0 + (int)__builtin_amdgcn_readfirstlane((int)f_field<QW, VL>(b, 0)) * uq;
-  const int nl = m.r0 + (int)__builtin_amdgcn_readlane((int)fl, ll) * uq;
+    for (int j = 0; j < NP; j++) if (j == jl) fl = f_field<QW, VL>(b, j);
+    n0 = m.r0 + (int)__builtin_amdgcn_readfirstlane((int)f_field<QW, VL>(b, 0)) * uq;
+    nl = m.r0 + (int)__builtin_amdgcn_readlane((int)fl, ll) * uq;
+  }
   if (n0 < 0) return false;
   const int s0 = f_slot(p, m, n0);
   if (f_slot(p, m, nl) != s0 || s0 >= K) return false;
@@ -2102,7 +2143,8 @@ __device__ __forceinline__ bool fast_series_end(const GridParams& p, const FastL
 
 // KR: 0 = LDS partials (rate, K > 64), 1 = register partials, 2 = the fused multi-aggregator
 // registers, 3 = register partials with the per-series output modes (sel_direct / dense_out).
-template <int F, int QW, int VL, int D, int KR>
+// REG: every row of the launch's tiles is regular (GridParams.reg): values only are loaded.
+template <int F, int QW, int VL, int D, int KR, bool REG = false>
 __global__ __launch_bounds__(256) void k_fast(GridParams p, const RowDesc* __restrict__ rows,
                                               const int64_t* __restrict__ srp, const int64_t* __restrict__ tbeg,
                                               const int64_t* __restrict__ tend) {
@@ -2137,16 +2179,16 @@ __global__ __launch_bounds__(256) void k_fast(GridParams p, const RowDesc* __res
   w.rend = (int32_t)(srp[tend[tile]] - w.r0);
   w.c0 = 0;
   w.sf = 0;
-  if (w.rend > 0) w.d = fdesc(rows, w.r0);
-  if (w.rend > 1) w.nd = fdesc(rows, w.r0 + 1);
+  if (w.rend > 0) w.d = fdesc_r<REG>(p, rows, w.r0);
+  if (w.rend > 1) w.nd = fdesc_r<REG>(p, rows, w.r0 + 1);
   WAVE_SYNC();
 
-  FRaw<QW, VL> buf[D];
-  FMeta meta[D];
+  FRaw<QW, VL, REG> buf[D];
+  std::conditional_t<REG, FMetaReg, FMeta> meta[D];
   bool redo = false;
 #pragma unroll
   for (int i = 0; i < D; i++) {
-    if (fast_issue<F, QW, VL>(p, rows, w, buf[i], meta[i]) == 2) redo = true;
+    if (fast_issue<F, QW, VL, REG>(p, rows, w, buf[i], meta[i]) == 2) redo = true;
   }
   if ((meta[0].bits & FM_OK) && !redo && lane == 0) atomicOr(&p.group_active[tgrp], 1u);
   bool have = false;
@@ -2201,13 +2243,15 @@ __global__ __launch_bounds__(256) void k_fast(GridParams p, const RowDesc* __res
             g = fgeom(p, x.base);
           }
           const int nv0 = (int)(mb & FM_NV);
+          uint32_t rf0 = 0, rstep = 0;
+          if constexpr (REG) { rf0 = meta[i].f0; rstep = meta[i].step; }
 #ifndef TSDBHIP_NO_ONEB
-          if (p.oneb && fast_chunk_oneb<F, QW, VL>(p, L, buf[i], g, nv0, K)) {
+          if (p.oneb && fast_chunk_oneb<F, QW, VL>(p, L, buf[i], g, nv0, K, rf0, rstep)) {
           } else
 #endif
-          if (nv0 >= CH) fast_chunk<F, QW, VL, true>(p, L, buf[i], g, nv0, K);
-          else fast_chunk<F, QW, VL, false>(p, L, buf[i], g, nv0, K);
-          if (fast_issue<F, QW, VL>(p, rows, w, buf[i], meta[i]) == 2) { redo = true; done = true; }
+          if (nv0 >= CH) fast_chunk<F, QW, VL, true>(p, L, buf[i], g, nv0, K, rf0, rstep);
+          else fast_chunk<F, QW, VL, false>(p, L, buf[i], g, nv0, K, rf0, rstep);
+          if (fast_issue<F, QW, VL, REG>(p, rows, w, buf[i], meta[i]) == 2) { redo = true; done = true; }
         }
       }
     }

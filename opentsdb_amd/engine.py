@@ -35,14 +35,14 @@ EXPORTS = [
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
-    "tsdbhip_regroup", "tsdbhip_append",
+    "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
 OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "TRACE", "DBG"]
+           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "TRACE", "DBG"]
 
 IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
@@ -152,6 +152,7 @@ def lib():
                                          C.POINTER(C.c_uint64)]
         L.tsdbhip_preagg_download.argtypes = [vp] + [C.c_void_p] * 7
         L.tsdbhip_debug_rows.argtypes = [vp] + [C.c_void_p] * 4
+        L.tsdbhip_debug_regular.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.tsdbhip_debug_index.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int)]
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_shard_bounds.argtypes = [C.POINTER(abi.Batch), C.c_int, C.c_int, C.c_void_p]
@@ -534,6 +535,17 @@ class Engine:
                                         amax.ctypes.data))
         k = nr.value
         return ndp[:k], flags[:k], lsb[:k], amax[:k]
+
+    def debug_regular(self):
+        """Test hook: (first_step [rows, 2] uint32 -- a regular row's first offset and step in
+        seconds, step 0 = not regular --, tiles on each class's regular list [2], tiles the last
+        query launched through k_fast's values-only form)."""
+        ns, nr, qb, vb = C.c_int64(), C.c_int64(), C.c_uint64(), C.c_uint64()
+        _check(lib().tsdbhip_batch_sizes(self.ctx, C.byref(ns), C.byref(nr), C.byref(qb), C.byref(vb)))
+        fs = np.zeros((max(1, nr.value), 2), np.uint32)
+        lists, launched = np.zeros(2, np.int64), C.c_int64()
+        _check(lib().tsdbhip_debug_regular(self.ctx, fs.ctypes.data, lists.ctypes.data, C.byref(launched)))
+        return fs[:nr.value], lists, launched.value
 
     def debug_index(self):
         """Test hook: (cnt, fused) of the last load's index -- cnt[0..10] rows by index class,
