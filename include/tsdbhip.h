@@ -285,6 +285,43 @@ typedef struct {
 } tsdbhip_append_info;
 int tsdbhip_append(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* series_index,
                    const uint8_t* series_new, tsdbhip_append_info* info /* may be NULL */);
+/* Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
+ * bytes.  Every resident row whose base time is < cutoff_s is evicted, of the
+ * visible series and of those the last tsdbhip_regroup excluded; a series' rows are in base
+ * order, so it loses a prefix.  A series left without a row stays resident with zero rows: the
+ * number of series, batch order and every group id are unchanged, so tsdbhip_regroup's ids and
+ * tsdbhip_append's series_index keep their meaning.  cutoff_s <= 0 evicts nothing.
+ * Afterwards the context answers every entry point as a fresh tsdbhip_load of the trimmed batch,
+ * followed by the tsdbhip_regroup that reproduces the present ids, would, bit for bit -- except
+ * that tsdbhip_debug_index and timing.index_ms describe the re-index pass below (zero rows when
+ * no row was suspect), cells of an earlier tsdbhip_rollup_run / tsdbhip_preagg_run are dropped,
+ * and a tsdbhip_load_cells compaction error whose row is evicted is dropped.  trim(c1) then
+ * trim(c2) equals trim(max(c1, c2)); a tsdbhip_append after a trim behaves as after a load of the
+ * trimmed batch, onto a series without rows included.
+ * A kept row that carries ROW_UNSORTED and whose series loses a row may owe the flag to an
+ * evicted row (a datapoint of an earlier row past this row's first): such rows are indexed
+ * again, in a descriptor array of their own as tsdbhip_append indexes a delta, and the walk over
+ * their series' kept rows sets the flag anew where it still holds.  No other row is read.
+ * pack_dead_pct < 0 (TSDB_TRIM_NO_PACK): no cell byte is read or written; the evicted rows'
+ * bytes are added to the dead bytes tsdbhip_append_info also reports.  pack_dead_pct >= 0: when
+ * the dead bytes after the eviction (both blobs) are at least that per cent of the used bytes
+ * (0: always), every loaded row's cells are copied into fresh blobs in descriptor order -- visible
+ * series in resident order, then the excluded ones --, 16-byte aligned with zero padding, and
+ * the dead bytes go to 0.  The pack is out of place: the fresh blobs (live bytes plus option
+ * APPEND_RESERVE per cent) are allocated beside the old ones before anything is queued.
+ * TSDB_E_ILLEGAL_ARGUMENT: a null context, pack_dead_pct > 100.  TSDB_E_NOT_IMPLEMENTED: a
+ * multi-device context, a rollup batch, a shard load.  TSDB_E_NOMEM: the fresh blobs do not fit
+ * beside the old ones (retry with TSDB_TRIM_NO_PACK).  An error leaves the resident batch as it
+ * was. */
+typedef struct {
+  int64_t rows_evicted, series_emptied, rows_reindexed;
+  uint64_t qual_capacity, val_capacity;     /* bytes the blobs have allocated after the call */
+  uint64_t qual_dead, val_dead;             /* dead bytes still in the blobs after the call */
+  uint64_t qual_reclaimed, val_reclaimed;   /* bytes this call gave back (0 without a pack) */
+  int32_t packed;                           /* this call re-laid the blobs */
+} tsdbhip_trim_info;
+#define TSDB_TRIM_NO_PACK (-1)
+int tsdbhip_trim(tsdbhip_ctx* ctx, int64_t cutoff_s, int32_t pack_dead_pct, tsdbhip_trim_info* info /* may be NULL */);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:
@@ -828,6 +865,15 @@ int tsdbhip_debug_rows(tsdbhip_ctx* ctx, uint32_t* ndp, uint32_t* flags, int32_t
  * list_tiles[2]: the tiles on each streaming class's regular list; *launched: the tiles the
  * last query ran through the values-only form of k_fast.  Any pointer may be null. */
 int tsdbhip_debug_regular(tsdbhip_ctx* ctx, uint32_t* first_step, int64_t* list_tiles, int64_t* launched);
+
+/* Test hook (no reference counterpart): the byte offsets of every loaded row's qualifiers and
+ * values in the device blobs, rows in descriptor order (the visible series' rows in resident
+ * order, then the excluded series'): tsdbhip_batch_sizes' rows plus the excluded ones.  Either
+ * pointer may be null. */
+int tsdbhip_debug_layout(tsdbhip_ctx* ctx, uint64_t* qoff, uint64_t* voff);
+/* ... and how many series and rows are loaded, those the last tsdbhip_regroup excluded included
+ * (what sizes tsdbhip_debug_layout's arrays).  Either pointer may be null. */
+int tsdbhip_debug_loaded(tsdbhip_ctx* ctx, int64_t* n_series, int64_t* n_rows);
 
 /* Test hook (no reference counterpart): the routes the last load's index took.  cnt[0..10] are
  * the rows of each index class (0: the sequential kernel's, 1 + 5 (4-byte qualifiers) + value

@@ -228,6 +228,25 @@ class AppendInfo(C.Structure):
     ]
 
 
+TRIM_NO_PACK = -1     # tsdbhip.h TSDB_TRIM_NO_PACK: tsdbhip_trim never re-lays the blobs
+
+
+class TrimInfo(C.Structure):
+    """tsdbhip_trim_info: what a tsdbhip_trim did to the resident batch."""
+    _fields_ = [
+        ("rows_evicted", C.c_int64),
+        ("series_emptied", C.c_int64),
+        ("rows_reindexed", C.c_int64),
+        ("qual_capacity", C.c_uint64),
+        ("val_capacity", C.c_uint64),
+        ("qual_dead", C.c_uint64),
+        ("val_dead", C.c_uint64),
+        ("qual_reclaimed", C.c_uint64),
+        ("val_reclaimed", C.c_uint64),
+        ("packed", C.c_int32),
+    ]
+
+
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,
               ds_all: bool = False, rate: bool = False, counter: bool = False,

@@ -416,6 +416,10 @@ struct tsdbhip_ctx {
   uint64_t qual_dead = 0, val_dead = 0;
   DevBuf ap_rows, ap_ent, ap_touch;    // the delta's descriptors, AppendParams.ent, the touched series
   HostBuf ap_stage;                    // ... page-locked (entries, then the touched list)
+  // tsdbhip_trim: the per-series skips, the suspect rows and their series; the suspects' staged
+  // descriptors and RegRows; the packed layout's row offsets
+  DevBuf tr_skip, tr_list, tr_ser, tr_rows, tr_reg, tr_qdst, tr_vdst;
+  HostBuf tr_stage;                    // ... page-locked (skips, then the suspect rows, then their series)
   std::vector<int64_t> h_srp;          // [n_series+1]
   std::vector<uint32_t> h_base;        // [n_rows]
   std::vector<uint32_t> h_ndp;         // [n_rows]
@@ -833,7 +837,8 @@ extern "C" int tsdbhip_init(int device, tsdbhip_ctx** out) {
 static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
-                    &c->reg, &c->reg2, &c->ap_reg})
+                    &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
+                    &c->tr_vdst})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -1167,6 +1172,8 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
     HIP_OK(hipEventRecord(c->ev[2], c->stream));
     HIP_OK(index_rows(c->qual.as<uint8_t>(), c->val.as<uint8_t>(), c->val2.as<uint8_t>(), c->rows.as<RowDesc>(), regp, ib,
                       ik, c->n_rows, c->err.as<int32_t>(), true, c->stream));
+    if (c->max_series_rows > 1)   // (the second pass has written every row's flags and RegRow anew: k_recede's go on again)
+      HIP_OK(index_recede(c->rows.as<RowDesc>(), regp, c->srp.as<int64_t>(), c->qual.as<uint8_t>(), c->n_series, c->stream));
     HIP_OK(hipEventRecord(c->ev[3], c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     (void)hipEventElapsedTime(&t_val2, c->ev[2], c->ev[3]);
@@ -3121,6 +3128,305 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   return rc;
 }
 
+// Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
+// bytes.  The descriptors are gathered as in tsdbhip_regroup, with a per-series
+// skip; kept rows whose ROW_UNSORTED an evicted row may have caused are indexed again in an array
+// of their own, as tsdbhip_append indexes a delta, and k_recede's walk runs over their series; the
+// pack copies every kept row's cells into fresh blobs in descriptor order.  Everything is
+// validated and allocated before anything is queued; the commit is the swap at the end.
+extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_pct, tsdbhip_trim_info* info) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  if (pack_dead_pct > 100) return fail(TSDB_E_ILLEGAL_ARGUMENT, "pack_dead_pct above 100");
+  MD_REFUSE(c, "tsdbhip_trim");
+  CtxLock lk(c);
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_trim over a rollup batch (tsdbhip_load_rollup)");
+  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
+  if (!c->regroup_ok && N > 0)
+    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_trim needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                        "tsdbhip_synth (a shard's groups are numbered globally)");
+  if (NR >= INT32_MAX) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_trim over 2^31 - 1 rows or more");
+  tsdbhip_trim_info ti{};
+  auto fill_info = [&]() {
+    ti.qual_capacity = c->qual.n;
+    ti.val_capacity = c->val.n;
+    ti.qual_dead = c->qual_dead;
+    ti.val_dead = c->val_dead;
+    if (info) *info = ti;
+  };
+  if (!c->regroup_ok || N == 0) { fill_info(); return 0; }
+  // ---- what goes: each series' rows are in base order, so it loses a prefix ----
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(c->tr_stage.ensure((size_t)N * 8 + (size_t)NR * 8 + (size_t)N * 4));
+  int64_t* const skip = reinterpret_cast<int64_t*>(c->tr_stage.p);
+  int64_t evicted = 0, emptied = 0;
+  uint64_t ev_q = 0, ev_v = 0, live_q = 0, live_v = 0;
+  bool need_v2_after = false;
+  auto wants_val2 = [](uint32_t f) { return (f & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2); };
+  std::vector<int64_t> n_srp(N + 1, 0);
+  for (int64_t i = 0; i < N; i++) {
+    const int64_t r0 = c->h_srp[i], r1 = c->h_srp[i + 1];
+    int64_t r = r0;
+    while (r < r1 && (int64_t)c->h_base[r] < cutoff_s) {
+      ev_q += align16(c->h_qlen[r]);
+      ev_v += align16(c->h_vlen[r]);
+      r++;
+    }
+    skip[i] = r - r0;
+    evicted += r - r0;
+    if (r > r0 && r == r1) emptied++;
+    for (; r < r1; r++) {
+      live_q += align16(c->h_qlen[r]);
+      live_v += align16(c->h_vlen[r]);
+      need_v2_after |= wants_val2(c->h_flags[r]);
+    }
+    n_srp[i + 1] = n_srp[i] + (r1 - r0 - skip[i]);
+  }
+  const int64_t NR2 = NR - evicted;
+  const uint64_t dead_q = c->qual_dead + ev_q, dead_v = c->val_dead + ev_v;
+  const uint64_t used = c->qual_bytes + c->val_bytes;
+  const bool do_pack =
+      pack_dead_pct >= 0 && (unsigned __int128)(dead_q + dead_v) * 100 >= (unsigned __int128)used * (uint64_t)pack_dead_pct;
+  if (evicted == 0 && !do_pack) { fill_info(); return 0; }   // (nothing changes)
+  // the suspect rows, as positions in the gathered array, and their series
+  int64_t* const sus = skip + N;
+  int32_t* const sus_ser = reinterpret_cast<int32_t*>(sus + NR);
+  int64_t n_sus = 0, n_ser = 0;
+  for (int64_t i = 0; i < N; i++) {
+    if (skip[i] == 0) continue;
+    const int64_t before = n_sus;
+    for (int64_t r = c->h_srp[i] + skip[i]; r < c->h_srp[i + 1]; r++)
+      if (c->h_flags[r] & ROW_UNSORTED) sus[n_sus++] = n_srp[i] + (r - c->h_srp[i] - skip[i]);
+    if (n_sus > before) sus_ser[n_ser++] = (int32_t)i;
+  }
+  // ---- allocations: nothing of the resident batch is released before the commit ----
+  struct Hold {   // what the call allocated and has not handed to the context
+    DevBuf q, v, v2;
+    ~Hold() { q.release(); v.release(); v2.release(); }
+  } hold;
+  auto nomem = [&](hipError_t e) {
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, "tsdbhip_trim: the packed blobs do not fit beside the resident ones "
+                                                         "(retry with TSDB_TRIM_NO_PACK)")
+                                    : fail(TSDB_E_HIP, std::string("tsdbhip_trim: ") + hipGetErrorString(e));
+  };
+  const bool had_val2 = c->val2.p != nullptr;
+  const bool pack_v2 = do_pack && had_val2 && need_v2_after;
+  if (pack_v2 && c->val2.n < c->qual_bytes)
+    return fail(TSDB_E_HIP, "tsdbhip_trim: the int16 value copy is shorter than the qualifier blob (internal)");
+  hipError_t he;
+  if (do_pack) {
+    const int64_t reserve = opt(OPT_APPEND_RESERVE) < 0 ? 50 : opt(OPT_APPEND_RESERVE);
+    auto grown = [&](uint64_t need) { return (size_t)(need + need / 100 * reserve + need % 100 * reserve / 100); };
+    if ((he = hold.q.ensure(grown(live_q + BLOB_SLACK))) != hipSuccess) return nomem(he);
+    if ((he = hold.v.ensure(grown(live_v + BLOB_SLACK))) != hipSuccess) return nomem(he);
+    if (pack_v2 && (he = hold.v2.ensure(hold.q.n)) != hipSuccess) return nomem(he);   // (val2 lives at qualifier offsets)
+    HIP_OK(c->tr_qdst.ensure((size_t)(NR2 + 1) * 8));
+    HIP_OK(c->tr_vdst.ensure((size_t)(NR2 + 1) * 8));
+  }
+  HIP_OK(c->tr_skip.ensure((size_t)N * 8));
+  HIP_OK(c->rows2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RegRow)));
+  HIP_OK(c->srp2.ensure((size_t)(N + 1) * 8));
+  HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  // the suspects' index pass: val2 by finish_load's rule, as tsdbhip_append has it for a delta.  A
+  // suspect row that needs the int16 copy had it written when it was first indexed, so the pass
+  // rewrites the same bytes; a copy allocated only because index_fused wants one goes with `idx_v2`.
+  DevBuf idx_v2;
+  struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_idx_v2{idx_v2};
+  const bool generic = opt_is(OPT_INDEX_GENERIC, 1);
+  bool fused = false;
+  uint8_t* v2p = c->val2.as<uint8_t>();   // (null when there is none)
+  const size_t qcap = c->qual.n;
+  if (n_sus) {
+    HIP_OK(c->tr_list.ensure((size_t)n_sus * 8));
+    HIP_OK(c->tr_ser.ensure((size_t)n_ser * 4));
+    HIP_OK(c->tr_rows.ensure((size_t)n_sus * sizeof(RowDesc)));
+    HIP_OK(c->tr_reg.ensure((size_t)n_sus * sizeof(RegRow)));
+    HIP_OK(c->hint.ensure(n_sus));
+    HIP_OK(c->ilist.ensure(n_sus * 4));
+    HIP_OK(c->icnt.ensure(32 * 4));
+    if (!generic) {
+      size_t fr = 0, tot = 0;
+      if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > qcap + ((size_t)8 << 30)) {
+        if (!v2p) {
+          if ((he = idx_v2.ensure(qcap)) != hipSuccess) return nomem(he);
+          v2p = idx_v2.as<uint8_t>();
+        }
+        fused = true;
+      }
+    }
+  }
+  // ---- queued work: the gather, the suspects' index and walk, the pack ----
+  struct Trace {
+    hipEvent_t e[5] = {};
+    bool on = false;
+    ~Trace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
+  } tr;
+  if (opt_is(OPT_TRACE, 1)) {
+    tr.on = true;
+    for (auto& x : tr.e) HIP_OK(hipEventCreate(&x));
+  }
+  auto mark = [&](int i) { return tr.on ? hipEventRecord(tr.e[i], c->stream) : hipSuccess; };
+  HIP_OK(mark(0));
+  HIP_OK(hipMemcpyAsync(c->tr_skip.p, skip, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+  TrimParams tp{};
+  tp.skip = c->tr_skip.as<int64_t>();
+  tp.srp_old = c->srp.as<int64_t>();
+  tp.rows_old = c->rows.as<RowDesc>();
+  tp.reg_old = c->reg.as<RegRow>();
+  tp.n_series = N;
+  tp.n_rows = NR2;
+  tp.srp_new = c->srp2.as<int64_t>();
+  tp.rows_new = c->rows2.as<RowDesc>();
+  tp.reg_new = c->reg2.as<RegRow>();
+  HIP_OK(trim_scan(tp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(launch_trim_gather(tp, c->stream));
+  HIP_OK(mark(1));
+  uint32_t idx_cnt[16] = {};
+  float t_index = 0;
+  if (n_sus) {
+    hipEvent_t* ev = c->ev;
+    HIP_OK(hipMemcpyAsync(c->tr_list.p, sus, (size_t)n_sus * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->tr_ser.p, sus_ser, (size_t)n_ser * 4, hipMemcpyHostToDevice, c->stream));
+    RowDesc* const drows = c->tr_rows.as<RowDesc>();
+    RegRow* const dreg = c->tr_reg.as<RegRow>();
+    HIP_OK(launch_trim_stage(tp.rows_new, c->tr_list.as<int64_t>(), n_sus, drows, c->stream));
+    HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
+    const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
+    const uint8_t* const qp = c->qual.as<uint8_t>();
+    const uint8_t* const vp = c->val.as<uint8_t>();
+    HIP_OK(hipEventRecord(ev[2], c->stream));
+    IndexClasses ik{};
+    if (fused)
+      HIP_OK(index_fused(qp, vp, v2p, drows, dreg, ib, n_sus, c->err.as<int32_t>(), &ik, c->stream));
+    else
+      HIP_OK(index_classes(qp, drows, ib, n_sus, &ik, c->stream));
+    if (!fused && ik.vle_capable && !generic && !v2p) {
+      if ((he = idx_v2.ensure(qcap)) != hipSuccess) return nomem(he);
+      v2p = idx_v2.as<uint8_t>();
+    }
+    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, dreg, ib, ik, n_sus, c->err.as<int32_t>(), generic, c->stream));
+    if (!generic) {
+      std::memcpy(idx_cnt, ik.cnt, sizeof(idx_cnt));
+      if (!fused) idx_cnt[IDX_C_FAIL] = 0;
+      if (!fused && ik.short_rows)
+        HIP_OK(hipMemcpyAsync(&idx_cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_OK(hipEventRecord(ev[3], c->stream));
+    HIP_OK(launch_trim_unstage(drows, dreg, c->tr_list.as<int64_t>(), n_sus, tp.rows_new, tp.reg_new, c->stream));
+    HIP_OK(launch_trim_recede(tp.rows_new, tp.reg_new, tp.srp_new, c->tr_ser.as<int32_t>(), n_ser, qp, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&t_index, ev[2], ev[3]);
+  }
+  HIP_OK(mark(2));
+  if (do_pack) {
+    HIP_OK(trim_pack_scan(tp.rows_new, NR2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp, &c->rg_tmp_bytes,
+                          c->stream));
+    // (the slack past the packed end, and the reserve, read as zeros)
+    HIP_OK(hipMemsetAsync(hold.q.as<uint8_t>() + live_q, 0, hold.q.n - live_q, c->stream));
+    HIP_OK(hipMemsetAsync(hold.v.as<uint8_t>() + live_v, 0, hold.v.n - live_v, c->stream));
+    if (pack_v2) HIP_OK(hipMemsetAsync(hold.v2.as<uint8_t>() + live_q, 0, hold.v2.n - live_q, c->stream));
+    TrimPackParams pp{};
+    pp.rows = tp.rows_new;
+    pp.n_rows = NR2;
+    pp.qdst = c->tr_qdst.as<uint64_t>();
+    pp.vdst = c->tr_vdst.as<uint64_t>();
+    pp.q_total = live_q;
+    pp.v_total = live_v;
+    pp.qual = c->qual.as<uint8_t>();
+    pp.val = c->val.as<uint8_t>();
+    pp.val2 = pack_v2 ? c->val2.as<uint8_t>() : nullptr;
+    pp.qual_new = hold.q.as<uint8_t>();
+    pp.val_new = hold.v.as<uint8_t>();
+    pp.val2_new = pack_v2 ? hold.v2.as<uint8_t>() : nullptr;
+    HIP_OK(launch_trim_pack(pp, c->stream));
+    HIP_OK(launch_trim_offsets(tp.rows_new, pp.qdst, pp.vdst, NR2, c->stream));
+  }
+  HIP_OK(mark(3));
+  // host mirrors from a download of the final descriptors, as tsdbhip_regroup refills them
+  if (NR2)
+    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
+  std::vector<RegRow> n_reg(NR2);
+  if (NR2) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR2 * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(mark(4));
+  std::vector<uint32_t> n_base(NR2), n_ndp(NR2), n_qlen(NR2), n_vlen(NR2), n_flags(NR2);
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (tr.on) {
+    float t[4] = {};
+    for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&t[i], tr.e[i], tr.e[i + 1]);
+    std::fprintf(stderr, "[trace trim] scan_gather %.3f reindex %.3f pack %.3f desc_download %.3f ms\n", t[0], t[1], t[2], t[3]);
+  }
+  {
+    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
+    for (int64_t r = 0; r < NR2; r++) {
+      n_base[r] = back[r].base;
+      n_ndp[r] = back[r].ndp;
+      n_qlen[r] = back[r].qlen;
+      n_vlen[r] = back[r].vlen;
+      n_flags[r] = back[r].flags;
+    }
+  }
+  // ---- commit: from here on the context holds the trimmed batch ----
+  std::swap(c->rows, c->rows2);
+  std::swap(c->reg, c->reg2);
+  c->h_reg.swap(n_reg);
+  std::swap(c->srp, c->srp2);
+  if (do_pack) {
+    ti.qual_reclaimed = c->qual_bytes - live_q;
+    ti.val_reclaimed = c->val_bytes - live_v;
+    ti.packed = 1;
+    std::swap(c->qual, hold.q);
+    std::swap(c->val, hold.v);
+    if (pack_v2) std::swap(c->val2, hold.v2);
+    else c->val2.release();   // (no kept row reads an int16 copy: a load of this batch would have none)
+    c->qual_bytes = live_q;
+    c->val_bytes = live_v;
+    c->qual_dead = c->val_dead = 0;
+  } else {
+    c->qual_dead = dead_q;
+    c->val_dead = dead_v;
+  }
+  c->h_srp.swap(n_srp);
+  c->h_base.swap(n_base);
+  c->h_ndp.swap(n_ndp);
+  c->h_qlen.swap(n_qlen);
+  c->h_vlen.swap(n_vlen);
+  c->h_flags.swap(n_flags);
+  c->n_rows_loaded = NR2;
+  c->n_rows = c->h_srp[c->n_series];
+  c->max_series_rows = 0;
+  for (int64_t i = 0; i < c->n_series; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
+  // tsdbhip_load_cells' compaction errors: an entry whose row is gone is dropped
+  if (!c->cmp_errs.empty() && evicted) {
+    std::vector<tsdbhip_ctx::CmpErr> kept;
+    for (const auto& e : c->cmp_errs)
+      if (e.base >= cutoff_s) kept.push_back(e);
+    c->cmp_errs.swap(kept);
+  }
+  std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
+  c->idx_fused = n_sus ? fused : false;
+  c->index_ms = t_index;
+  // what a load invalidates of the state that depends on the rows
+  c->none_tiles_ready = false;
+  c->acct_valid = false;
+  c->seqd_valid = false;
+  c->row_ser_valid = false;
+  c->n_grouped = -1;
+  c->mdp_valid = false;
+  c->ro_meta_valid = false;
+  c->lc_valid = false;
+  c->calc_valid = false;
+  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the batch they came from)
+  c->pg.cells = 0;
+  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  const int rc = finish_classes(c);
+  ti.rows_evicted = evicted;
+  ti.series_emptied = emptied;
+  ti.rows_reindexed = n_sus;
+  fill_info();
+  return rc;
+}
+
 extern "C" int tsdbhip_batch_sizes(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_rows, uint64_t* qual_bytes,
                                    uint64_t* val_bytes) {
   if (c && c->md) return tsdb::md_batch_sizes(c, n_series, n_rows, qual_bytes, val_bytes);
@@ -3274,6 +3580,33 @@ extern "C" int tsdbhip_debug_regular(tsdbhip_ctx* c, uint32_t* first_step, int64
   if (list_tiles)
     for (int cls = 0; cls < 2; cls++) list_tiles[cls] = (int64_t)c->tl[cls][3].size();
   if (launched) *launched = c->reg_launched;
+  return 0;
+}
+
+// Test hook: where every loaded row's cells lie in the blobs, rows in descriptor order.
+extern "C" int tsdbhip_debug_layout(tsdbhip_ctx* c, uint64_t* qoff, uint64_t* voff) {
+  MD_REFUSE(c, "tsdbhip_debug_layout");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_debug_layout over a rollup batch (tsdbhip_load_rollup)");
+  CtxLock lk(c);
+  HIP_OK(hipSetDevice(c->device));
+  const int64_t nr = std::max(c->n_rows, c->n_rows_loaded);
+  std::vector<RowDesc> rd(nr);
+  if (nr) HIP_OK(hipMemcpy(rd.data(), c->rows.p, nr * sizeof(RowDesc), hipMemcpyDeviceToHost));
+  for (int64_t r = 0; r < nr; r++) {
+    if (qoff) qoff[r] = rd[r].qoff;
+    if (voff) voff[r] = rd[r].voff;
+  }
+  return 0;
+}
+
+extern "C" int tsdbhip_debug_loaded(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_rows) {
+  MD_REFUSE(c, "tsdbhip_debug_loaded");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_debug_loaded over a rollup batch (tsdbhip_load_rollup)");
+  CtxLock lk(c);
+  if (n_series) *n_series = std::max(c->n_series, c->n_series_loaded);
+  if (n_rows) *n_rows = std::max(c->n_rows, c->n_rows_loaded);
   return 0;
 }
 

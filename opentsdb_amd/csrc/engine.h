@@ -554,6 +554,47 @@ hipError_t launch_append(const AppendParams& p, hipStream_t s);
 // k_recede over the series at new positions touched[0 .. n): ROW_UNSORTED on delta rows only
 hipError_t launch_append_recede(const AppendParams& p, const int32_t* touched, int64_t n, const uint8_t* qual,
                                 hipStream_t s);
+// tsdbhip_trim (k_trim.hip): every loaded series without the first skip[i] of its rows; the
+// series' order and groups stay.
+struct TrimParams {
+  const int64_t* skip;        // [n_series] rows the series at position i loses at its front
+  const int64_t* srp_old;     // [n_series + 1] current series_row_ptr (every loaded series)
+  const RowDesc* rows_old;    // [n_rows_old]
+  const RegRow* reg_old;      // [n_rows_old]
+  int64_t n_series;
+  int64_t n_rows;             // rows after the trim
+  int64_t* srp_new;           // [n_series + 1] (out, trim_scan)
+  RowDesc* rows_new;          // [n_rows] (out)
+  RegRow* reg_new;            // [n_rows] (out)
+};
+hipError_t trim_scan(const TrimParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_trim_gather(const TrimParams& p, hipStream_t s);
+// the suspect rows list[0 .. n) of `rows` as unindexed descriptors in `out`, and back after the index pass
+hipError_t launch_trim_stage(const RowDesc* rows, const int64_t* list, int64_t n, RowDesc* out, hipStream_t s);
+hipError_t launch_trim_unstage(const RowDesc* in, const RegRow* reg_in, const int64_t* list, int64_t n, RowDesc* rows,
+                               RegRow* reg, hipStream_t s);
+// k_recede over the series at positions series[0 .. n): any of their rows may be flagged
+hipError_t launch_trim_recede(RowDesc* rows, RegRow* reg, const int64_t* srp, const int32_t* series, int64_t n,
+                              const uint8_t* qual, hipStream_t s);
+// the pack: rows' cells copied into fresh blobs in descriptor order, 16-byte aligned.  qdst / vdst
+// are the exclusive scans of the aligned lengths, n_rows + 1 entries (trim_pack_scan).
+struct TrimPackParams {
+  const RowDesc* rows;        // [n_rows] qoff / voff into the old blobs
+  int64_t n_rows;
+  const uint64_t* qdst;       // [n_rows + 1]
+  const uint64_t* vdst;       // [n_rows + 1]
+  uint64_t q_total, v_total;  // qdst[n_rows], vdst[n_rows]
+  const uint8_t* qual;
+  const uint8_t* val;
+  const uint8_t* val2;        // null: no int16 copy to carry over
+  uint8_t* qual_new;
+  uint8_t* val_new;
+  uint8_t* val2_new;
+};
+hipError_t trim_pack_scan(const RowDesc* rows, int64_t n_rows, uint64_t* qdst, uint64_t* vdst, void** tmp,
+                          size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_trim_pack(const TrimPackParams& p, hipStream_t s);
+hipError_t launch_trim_offsets(RowDesc* rows, const uint64_t* qdst, const uint64_t* vdst, int64_t n_rows, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

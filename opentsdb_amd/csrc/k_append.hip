@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "engine.h"
+#include "recede.h"
 
 namespace tsdb {
 
@@ -82,15 +83,7 @@ struct AppendCount {
   }
 };
 
-__device__ __forceinline__ int64_t append_qual_ms(const uint8_t* q, uint32_t pos, int qw) {
-  if (qw == 4 || (qw != 2 && (q[pos] & 0xF0) == 0xF0)) {
-    const uint32_t w = ((uint32_t)q[pos] << 24) | ((uint32_t)q[pos + 1] << 16) | ((uint32_t)q[pos + 2] << 8) | q[pos + 3];
-    return (w & 0x0FFFFFC0u) >> 6;
-  }
-  return (int64_t)(((((uint32_t)q[pos] << 8) | q[pos + 1]) >> 4) & 0xFFF) * 1000;
-}
-
-// k_recede's walk (k_index.hip) over the touched series of the gathered descriptors.  A resident
+// k_recede's walk (recede.h) over the touched series of the gathered descriptors.  A resident
 // row may already carry k_recede's own ROW_UNSORTED; its latest datapoint is then taken as the
 // maximum over its cells, which for a cell sorted in itself is its last one, as k_recede read it.
 __global__ __launch_bounds__(256) void k_recede_touched(AppendParams p, const int32_t* __restrict__ touched, int64_t n,
@@ -100,33 +93,7 @@ __global__ __launch_bounds__(256) void k_recede_touched(AppendParams p, const in
   const int64_t s = touched[t];
   const int64_t r0 = p.srp_new[s], r1 = p.srp_new[s + 1];
   const int64_t first_delta = r1 - (int64_t)(p.ent[s].w & ~APPEND_REPLACE);
-  int64_t M = INT64_MIN;   // latest datapoint of the earlier rows
-  for (int64_t r = r0; r < r1; r++) {
-    const RowDesc d = p.rows_new[r];
-    if ((d.flags & ROW_ERR) || d.ndp == 0) continue;
-    const uint8_t* q = qual + d.qoff;
-    const int qw = d.flags & ROW_QW_MASK;
-    const int64_t b = (int64_t)d.base * 1000;
-    const int64_t first = b + append_qual_ms(q, 0, qw);
-    int64_t mx;
-    if (!(d.flags & ROW_UNSORTED) && (qw == 2 || qw == 4)) {
-      mx = b + append_qual_ms(q, (d.ndp - 1) * (uint32_t)qw, qw);
-    } else {   // a mixed-width row: walk to its last cell; a row out of order: its latest cell
-      mx = INT64_MIN;
-      uint32_t pos = 0;
-      for (uint32_t i = 0; i < d.ndp && pos < d.qlen; i++) {
-        const int w = qw ? qw : ((q[pos] & 0xF0) == 0xF0 ? 4 : 2);
-        const int64_t tt = b + append_qual_ms(q, pos, qw);
-        mx = (d.flags & ROW_UNSORTED) ? max(mx, tt) : tt;
-        pos += w;
-      }
-    }
-    if (r >= first_delta && first <= M) {
-      p.rows_new[r].flags = d.flags | ROW_UNSORTED;
-      p.reg_new[r] = RegRow{0u, 0u};   // (an unsorted row is not regular)
-    }
-    M = max(M, mx);
-  }
+  recede_series(p.rows_new, p.reg_new, r0, r1, first_delta, qual);
 }
 
 }  // namespace

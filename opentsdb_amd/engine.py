@@ -35,7 +35,8 @@ EXPORTS = [
     "tsdbhip_batch_range_sizes", "tsdbhip_batch_download_range", "tsdbhip_expr_sync", "tsdbhip_init_devices",
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
-    "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular",
+    "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
+    "tsdbhip_debug_loaded",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -119,6 +120,9 @@ def lib():
         L.tsdbhip_load.argtypes = [vp, C.POINTER(abi.Batch)]
         L.tsdbhip_regroup.argtypes = [vp, C.c_void_p, C.c_int64]
         L.tsdbhip_append.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.AppendInfo)]
+        L.tsdbhip_trim.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
+        L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
+        L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
         L.tsdbhip_batch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]
@@ -396,6 +400,15 @@ class Engine:
                                     new.ctypes.data if len(new) else None, C.byref(info)))
         return info
 
+    def trim(self, cutoff_s: int, pack_dead_pct: int = abi.TRIM_NO_PACK) -> abi.TrimInfo:
+        """tsdbhip_trim: every resident row with a base time below cutoff_s is evicted (series and
+        ids stay, a series may be left without rows).  pack_dead_pct < 0 never moves a cell byte;
+        otherwise the blobs are re-laid without their dead bytes when those are at least that per
+        cent of the used bytes (0: always)."""
+        info = abi.TrimInfo()
+        _check(lib().tsdbhip_trim(self.ctx, int(cutoff_s), int(pack_dead_pct), C.byref(info)))
+        return info
+
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""
         _check(lib().tsdbhip_load_cells(self.ctx, C.byref(cb.c)))
@@ -546,6 +559,15 @@ class Engine:
         lists, launched = np.zeros(2, np.int64), C.c_int64()
         _check(lib().tsdbhip_debug_regular(self.ctx, fs.ctypes.data, lists.ctypes.data, C.byref(launched)))
         return fs[:nr.value], lists, launched.value
+
+    def debug_layout(self):
+        """Test hook: (qoff, voff) of every loaded row in the device blobs, rows in descriptor
+        order -- the visible series' rows in resident order, then the excluded series'."""
+        nr = C.c_int64()
+        _check(lib().tsdbhip_debug_loaded(self.ctx, None, C.byref(nr)))
+        qoff, voff = np.zeros(max(1, nr.value), np.uint64), np.zeros(max(1, nr.value), np.uint64)
+        _check(lib().tsdbhip_debug_layout(self.ctx, qoff.ctypes.data, voff.ctypes.data))
+        return qoff[:nr.value], voff[:nr.value]
 
     def debug_index(self):
         """Test hook: (cnt, fused) of the last load's index -- cnt[0..10] rows by index class,

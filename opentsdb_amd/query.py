@@ -631,6 +631,23 @@ class ResidentSpans:
         self.scan_end_s = scan_end_s
         return info
 
+    def trim(self, scan_start_s: int, pack_dead_pct: int = 50):
+        """Move the resident range's start to scan_start_s without a reload (Engine.trim,
+        tsdbhip_trim): the rows a scan of [scan_start_s, scan_end_s) no longer returns -- those
+        with a base time below scan_start_s -- are evicted.  A span left without rows stays, as
+        extend keeps row-less ones, so the series' indices keep their meaning.  The blobs are
+        re-laid without their dead bytes once those reach pack_dead_pct per cent of the used
+        bytes; the default of 50 is a policy that mirrors the reserve tsdbhip_append grows by
+        (option APPEND_RESERVE), not a measured optimum.  Returns the engine's abi.TrimInfo."""
+        if scan_start_s < self.scan_start_s:
+            raise ValueError(f"the resident range starts at {self.scan_start_s}: it cannot grow back to {scan_start_s}")
+        if scan_start_s >= self.scan_end_s:
+            raise ValueError(f"the resident range ends at {self.scan_end_s}: a start of {scan_start_s} leaves it empty")
+        info = self.engine.trim(scan_start_s, pack_dead_pct)
+        self.spans = [(sk, [r for r in rows if r[0] >= scan_start_s]) for sk, rows in self.spans]
+        self.scan_start_s = scan_start_s
+        return info
+
     def run(self, query: TsdbQuery):
         """DataPoints[] of the query, keyed as TsdbQuery._run_raw keys them."""
         if query.store is not self.store or query.metric != self.metric:
