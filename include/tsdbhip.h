@@ -275,7 +275,7 @@ int tsdbhip_regroup(tsdbhip_ctx* ctx, const int32_t* group_id, int64_t n_series)
  * old index outside [0, N), a new series' id below -2, the delta's own batch invariants failing.
  * TSDB_E_NOT_IMPLEMENTED: a multi-device context, a rollup batch, a shard load; a delta row
  * earlier than its series' last resident row (back-fill, or replacing a row that is not the
- * last): reload instead.  TSDB_E_NOMEM: the grown blobs do not fit beside the old ones.
+ * last): tsdbhip_upsert, or reload instead.  TSDB_E_NOMEM: the grown blobs do not fit beside the old ones.
  * An error leaves the resident batch as it was.  A delta without series is a no-op. */
 typedef struct {
   int64_t series_added, rows_added, rows_replaced;
@@ -285,6 +285,45 @@ typedef struct {
 } tsdbhip_append_info;
 int tsdbhip_append(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* series_index,
                    const uint8_t* series_new, tsdbhip_append_info* info /* may be NULL */);
+/* Rows upserted anywhere in the resident batch, without a reload: tsdbhip_append
+ * without its restriction to what a tail scan yields.  `delta`, `series_index` and `series_new`
+ * mean exactly what they mean for tsdbhip_append: indices in the batch AFTER the call, N' = N +
+ * #new; resident series keep their relative order; a new series takes delta->group_id[i], a
+ * resident series keeps its group or its exclusion.
+ * An unrestricted upsert by (series, base time): a delta row whose base time equals that of ANY
+ * resident row of its series REPLACES that row (it is not merged); every other delta row is
+ * inserted where base order puts it -- before the series' first row, between two rows, after the
+ * last, or onto a series with zero rows.  A series' delta rows may come in any order; rows of the
+ * delta that share (series, base) are merged first, as tsdbhip_load merges them.  This is what
+ * late datapoints for a closed hour, the compaction queue's rewrite of a closed hour's row, a
+ * fix_duplicates repair and a collector's back-fill need.  Rows cannot be removed (tsdbhip_trim).
+ * Afterwards the context answers every entry point as a fresh tsdbhip_load of the merged batch,
+ * followed by the tsdbhip_regroup that reproduces the present ids, would, bit for bit, with
+ * tsdbhip_append's exceptions: tsdbhip_debug_index and timing.index_ms describe this call's
+ * index passes (the delta's plus the suspects', below), cells of an earlier tsdbhip_rollup_run /
+ * tsdbhip_preagg_run are dropped, a tsdbhip_load_cells compaction error is renumbered (dropped
+ * when the delta brings its (series, base)), and a malformed delta cell is reported by the first
+ * query that reads it.  A tail-shaped delta leaves the state tsdbhip_append leaves.
+ * The delta's cells go to the blobs' tail, 16-byte aligned, and the blobs grow as in
+ * tsdbhip_append (option APPEND_RESERVE, allocated beside the old ones and swapped at the commit).
+ * A replaced row's bytes become dead bytes wherever the row sat (qual_dead / val_dead: a later
+ * tsdbhip_trim with a pack reclaims them).  rows_added counts the delta rows that replaced
+ * nothing.  An inserted or replacing row may make a later row of its series ROW_UNSORTED: the walk
+ * over the touched series may flag any of their rows.  A replaced row may have been the cause of a
+ * later row's flag: kept resident rows that carry ROW_UNSORTED and lie after their series'
+ * earliest replaced row are indexed again first, as tsdbhip_trim indexes its suspects
+ * (rows_reindexed; 0 for a delta that only inserts).
+ * TSDB_E_ILLEGAL_ARGUMENT, TSDB_E_NOMEM and TSDB_E_NOT_IMPLEMENTED for a multi-device context, a
+ * rollup batch and a shard load are tsdbhip_append's; there is no back-fill refusal.  An error
+ * leaves the resident batch as it was.  A delta without series is a no-op. */
+typedef struct {
+  int64_t series_added, rows_added, rows_replaced, rows_reindexed;
+  uint64_t qual_capacity, val_capacity;   /* as tsdbhip_append_info */
+  uint64_t qual_dead, val_dead;
+  int32_t grew;
+} tsdbhip_upsert_info;
+int tsdbhip_upsert(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* series_index,
+                   const uint8_t* series_new, tsdbhip_upsert_info* info /* may be NULL */);
 /* Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
  * bytes.  Every resident row whose base time is < cutoff_s is evicted, of the
  * visible series and of those the last tsdbhip_regroup excluded; a series' rows are in base

@@ -228,7 +228,22 @@ class AppendInfo(C.Structure):
     ]
 
 
-TRIM_NO_PACK = -1     # tsdbhip.h TSDB_TRIM_NO_PACK: tsdbhip_trim never re-lays the blobs
+class UpsertInfo(C.Structure):
+    """tsdbhip_upsert_info: what a tsdbhip_upsert did to the resident batch."""
+    _fields_ = [
+        ("series_added", C.c_int64),
+        ("rows_added", C.c_int64),
+        ("rows_replaced", C.c_int64),
+        ("rows_reindexed", C.c_int64),
+        ("qual_capacity", C.c_uint64),
+        ("val_capacity", C.c_uint64),
+        ("qual_dead", C.c_uint64),
+        ("val_dead", C.c_uint64),
+        ("grew", C.c_int32),
+    ]
+
+
+TRIM_NO_PACK = -1    # tsdbhip.h TSDB_TRIM_NO_PACK: tsdbhip_trim never re-lays the blobs
 
 
 class TrimInfo(C.Structure):

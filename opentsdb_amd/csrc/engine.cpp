@@ -416,6 +416,9 @@ struct tsdbhip_ctx {
   uint64_t qual_dead = 0, val_dead = 0;
   DevBuf ap_rows, ap_ent, ap_touch;    // the delta's descriptors, AppendParams.ent, the touched series
   HostBuf ap_stage;                    // ... page-locked (entries, then the touched list)
+  // tsdbhip_upsert: each delta row's series, its rank among the series' resident rows, whether it
+  // replaces one, the scan of that (UpsertRankParams / UpsertParams)
+  DevBuf up_dser, up_lb, up_hit, up_S;
   // tsdbhip_trim: the per-series skips, the suspect rows and their series; the suspects' staged
   // descriptors and RegRows; the packed layout's row offsets
   DevBuf tr_skip, tr_list, tr_ser, tr_rows, tr_reg, tr_qdst, tr_vdst;
@@ -838,7 +841,7 @@ static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
                     &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
-                    &c->tr_vdst})
+                    &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -2703,16 +2706,25 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
 // kept resident descriptors and the delta's into the series order a fresh load of the merged
 // batch, regrouped to the present ids, would have.  Everything is validated and allocated before
 // the resident batch changes; the commit is the swap at the end, as in tsdbhip_regroup.
-extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index,
-                              const uint8_t* series_new, tsdbhip_append_info* info) {
-  if (!c || !delta) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
-  MD_REFUSE(c, "tsdbhip_append");
+//
+// tsdbhip_upsert is the same call without the restriction to a tail scan: a delta
+// row goes wherever base order puts it in its series and replaces the resident row of its base.
+// Which rows replace one is found on the device (k_upsert_rank), the gather is k_upsert's merge of
+// two sorted lists, kept rows whose ROW_UNSORTED a replaced row may have caused are indexed again
+// as tsdbhip_trim indexes its suspects, and k_recede's walk may flag any row of a touched series.
+struct MergeInfo {
+  int64_t series_added = 0, rows_added = 0, rows_replaced = 0, rows_reindexed = 0;
+  bool grew = false;
+};
+static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index, const uint8_t* series_new,
+                       const bool upsert, MergeInfo* mi) {
+  const std::string fn = upsert ? "tsdbhip_upsert" : "tsdbhip_append";
   CtxLock lk(c);
-  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_append over a rollup batch (tsdbhip_load_rollup)");
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, fn + " over a rollup batch (tsdbhip_load_rollup)");
   const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
   if (!c->regroup_ok)
-    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_append needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
-                                        "tsdbhip_synth (a shard's groups are numbered globally)");
+    return fail(TSDB_E_NOT_IMPLEMENTED, fn + " needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                             "tsdbhip_synth (a shard's groups are numbered globally)");
   // the delta's own batch invariants (load_body's checks)
   const tsdbhip_batch* b = delta;
   if (b->n_series < 0 || b->n_rows < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
@@ -2730,19 +2742,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
     if (b->row_qual_off[r + 1] - b->row_qual_off[r] > 0xFFFFFFFFull || b->row_val_off[r + 1] - b->row_val_off[r] > 0xFFFFFFFFull)
       return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
   }
-  auto fill_info = [&](int64_t sa, int64_t ra, int64_t rr, bool grew) {
-    if (!info) return;
-    info->series_added = sa;
-    info->rows_added = ra;
-    info->rows_replaced = rr;
-    info->qual_capacity = c->qual.n;
-    info->val_capacity = c->val.n;
-    info->qual_dead = c->qual_dead;
-    info->val_dead = c->val_dead;
-    info->grew = grew ? 1 : 0;
-  };
   const int64_t D = b->n_series;
-  if (D == 0) { fill_info(0, 0, 0, false); return 0; }
+  if (D == 0) return 0;
   // rows of the delta that share (series, base) merge first, as at load
   MergedBatch mb;
   if (merge_same_base(b, mb)) b = &mb.m;
@@ -2780,7 +2781,9 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   std::vector<int64_t> drow;            // delta rows in staging order: series by series, by base
   std::vector<int32_t> d0(D), dn(D);
   std::vector<uint8_t> repl(D, 0);
+  std::vector<int32_t> dser;            // upsert: the resident position of each staged row's series (-1: new)
   drow.reserve(DR);
+  if (upsert) dser.assign(DR, -1);
   int64_t n_repl = 0;
   uint64_t dead_q = 0, dead_v = 0;
   for (int64_t i = 0; i < D; i++) {
@@ -2792,6 +2795,10 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
                      [&](int64_t x, int64_t y) { return b->row_base_time[x] < b->row_base_time[y]; });
     if (series_new[i] || r1 == r0) continue;
     const int64_t p = pos[old_of[series_index[i]]];
+    if (upsert) {   // (what each row does is found on the device: k_upsert_rank)
+      std::fill(dser.begin() + d0[i], dser.begin() + d0[i] + dn[i], (int32_t)p);
+      continue;
+    }
     if (c->h_srp[p + 1] == c->h_srp[p]) continue;
     const int64_t last = c->h_srp[p + 1] - 1;
     const uint32_t first_base = b->row_base_time[drow[d0[i]]];
@@ -2799,8 +2806,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
       return fail(TSDB_E_NOT_IMPLEMENTED,
                   "tsdbhip_append: a delta row of series " + std::to_string(series_index[i]) + " (base " +
                       std::to_string(first_base) + ") lies before the series' last resident row (base " +
-                      std::to_string(c->h_base[last]) + "): back-fill and replacing a row that is not the last need a "
-                      "reload (tsdbhip_load of the merged batch)");
+                      std::to_string(c->h_base[last]) + "): back-fill and replacing a row that is not the last need "
+                      "tsdbhip_upsert, or a reload (tsdbhip_load of the merged batch)");
     if (first_base == c->h_base[last]) {
       repl[i] = 1;
       n_repl++;
@@ -2808,7 +2815,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
       dead_v += align16(c->h_vlen[last]);
     }
   }
-  const int64_t NR2 = NR + DR - n_repl;
+  // (upsert: an upper bound for the allocations until the device has said which rows replace one)
+  int64_t NR2 = NR + DR - n_repl;
   // the groups: resident series keep theirs, new ones take the delta's ids
   const int64_t G_old = c->n_groups;
   int32_t maxg = -1;
@@ -2848,7 +2856,7 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   // (not zero-filled first and not single-threaded: for a large delta this pass is the call's cost)
   const size_t hq_n = qtot - q0, hv_n = vtot - v0;
   std::unique_ptr<uint8_t[]> hq(new (std::nothrow) uint8_t[hq_n + 1]), hv(new (std::nothrow) uint8_t[hv_n + 1]);
-  if (!hq || !hv) return fail(TSDB_E_NOMEM, "tsdbhip_append: no host memory to stage the delta's cells");
+  if (!hq || !hv) return fail(TSDB_E_NOMEM, fn + ": no host memory to stage the delta's cells");
   pack_cells(hq.get(), hv.get(), b, drow.data(), rd.data(), DR, q0, v0);
   HIP_OK(hipSetDevice(c->device));
   // ---- allocations: nothing of the resident batch is released before the commit ----
@@ -2862,8 +2870,8 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   const bool grow_q = !c->qual.p || qtot + BLOB_SLACK > c->qual.n, grow_v = !c->val.p || vtot + BLOB_SLACK > c->val.n;
   auto nomem = [&](hipError_t e) {
     (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, "tsdbhip_append: the grown blobs do not fit beside the resident ones")
-                                    : fail(TSDB_E_HIP, std::string("tsdbhip_append: ") + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, fn + ": the grown blobs do not fit beside the resident ones")
+                                    : fail(TSDB_E_HIP, fn + ": " + hipGetErrorString(e));
   };
   hipError_t he;
   if (grow_q && (he = hold.q.ensure(grown(qtot + BLOB_SLACK))) != hipSuccess) return nomem(he);
@@ -2886,6 +2894,12 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   HIP_OK(c->hint.ensure(std::max<int64_t>(1, DR)));
   HIP_OK(c->ilist.ensure(std::max<int64_t>(1, DR) * 4));
   HIP_OK(c->icnt.ensure(32 * 4));
+  if (upsert) {
+    HIP_OK(c->up_dser.ensure(std::max<size_t>(1, (size_t)DR) * 4));
+    HIP_OK(c->up_lb.ensure(std::max<size_t>(1, (size_t)DR) * 4));
+    HIP_OK(c->up_hit.ensure((size_t)(DR + 1) * 4));
+    HIP_OK(c->up_S.ensure((size_t)(DR + 1) * 4));
+  }
   // val2 for the delta's index pass, by finish_load's rule; a copy the resident rows lacked is
   // allocated at the qualifier blob's capacity (resident rows never read it)
   const bool generic = opt_is(OPT_INDEX_GENERIC, 1);
@@ -2906,7 +2920,7 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   // option TRACE: the stages by hipEvents of the call's own (stream time between stage ends, the
   // host work in between included), on stderr
   struct Trace {
-    hipEvent_t e[6] = {};
+    hipEvent_t e[11] = {};   // (6 .. 10: tsdbhip_upsert's stages)
     bool on = false;
     ~Trace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
   } tr;
@@ -2951,16 +2965,17 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
       n_group[i] = (int32_t)k;
       if (di >= 0 && dn[di] > 0) touched[n_touched++] = (int32_t)i;
     }
-    for (int64_t i = 0; i < N2; i++) {
+    for (int64_t i = 0; i < N2 && !upsert; i++) {   // (upsert: once the replaced rows are known)
       const int64_t res = ent[i].x >= 0 ? c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x] : 0;
       n_srp[i + 1] = n_srp[i] + res - ((ent[i].w & APPEND_REPLACE) ? 1 : 0) + (ent[i].w & ~APPEND_REPLACE);
     }
   }
-  if (n_srp[N2] != NR2) return fail(TSDB_E_HIP, "tsdbhip_append: row count mismatch (internal)");
+  if (!upsert && n_srp[N2] != NR2) return fail(TSDB_E_HIP, "tsdbhip_append: row count mismatch (internal)");
   HIP_OK(hipMemcpyAsync(c->ap_ent.p, ent, (size_t)N2 * sizeof(int4), hipMemcpyHostToDevice, c->stream));
   if (n_touched)
     HIP_OK(hipMemcpyAsync(c->ap_touch.p, touched, (size_t)n_touched * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));   // (rd, hq, hv are pageable: staged before they leave scope)
+  if (upsert && DR) HIP_OK(hipMemcpyAsync(c->up_dser.p, dser.data(), (size_t)DR * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));   // (rd, hq, hv, dser are pageable: staged before they leave scope)
   // index only the delta: its descriptors in their own array, the blob base pointers as they are
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
   const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
@@ -2968,26 +2983,55 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   RegRow* dreg = c->ap_reg.as<RegRow>();
   HIP_OK(mark(2));
   HIP_OK(hipEventRecord(ev[2], c->stream));
-  IndexClasses ik{};
-  uint32_t idx_cnt[16] = {};
-  if (DR) {
+  // one index pass over descriptors in an array of their own, under finish_load's rules: the
+  // delta's rows and, in tsdbhip_upsert, the suspect rows
+  auto index_pass = [&](RowDesc* rows_, RegRow* reg_, int64_t n, const IndexBufs& ib_, IndexClasses& ik_, uint32_t* cnt) -> int {
     if (fused)
-      HIP_OK(index_fused(qp, vp, v2p, drows, dreg, ib, DR, c->err.as<int32_t>(), &ik, c->stream));
+      HIP_OK(index_fused(qp, vp, v2p, rows_, reg_, ib_, n, c->err.as<int32_t>(), &ik_, c->stream));
     else
-      HIP_OK(index_classes(qp, drows, ib, DR, &ik, c->stream));
-    if (!fused && ik.vle_capable && !generic && !v2p) {
+      HIP_OK(index_classes(qp, rows_, ib_, n, &ik_, c->stream));
+    if (!fused && ik_.vle_capable && !generic && !v2p) {
       if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
       v2p = hold.v2.as<uint8_t>();
     }
-    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, dreg, ib, ik, DR, c->err.as<int32_t>(), generic, c->stream));
+    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, rows_, reg_, ib_, ik_, n, c->err.as<int32_t>(), generic, c->stream));
     if (!generic) {
-      std::memcpy(idx_cnt, ik.cnt, sizeof(idx_cnt));
-      if (!fused) idx_cnt[IDX_C_FAIL] = 0;
-      if (!fused && ik.short_rows)
-        HIP_OK(hipMemcpyAsync(&idx_cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
+      std::memcpy(cnt, ik_.cnt, 16 * sizeof(uint32_t));
+      if (!fused) cnt[IDX_C_FAIL] = 0;
+      if (!fused && ik_.short_rows)
+        HIP_OK(hipMemcpyAsync(&cnt[IDX_C_FAIL], ib_.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
     }
+    return 0;
+  };
+  IndexClasses ik{};
+  uint32_t idx_cnt[16] = {};
+  if (DR) {
+    const int rc = index_pass(drows, dreg, DR, ib, ik, idx_cnt);
+    if (rc) return rc;
   }
   HIP_OK(hipEventRecord(ev[3], c->stream));
+  // tsdbhip_upsert: where each delta row goes among its series' resident rows
+  std::vector<int32_t> h_lb, h_hit;
+  if (upsert) {
+    UpsertRankParams rp{};
+    rp.dser = c->up_dser.as<int32_t>();
+    rp.srp_old = c->srp.as<int64_t>();
+    rp.rows_old = c->rows.as<RowDesc>();
+    rp.rows_delta = drows;
+    rp.n_delta = DR;
+    rp.lb = c->up_lb.as<int32_t>();
+    rp.hit = c->up_hit.as<int32_t>();
+    HIP_OK(launch_upsert_rank(rp, c->stream));
+    HIP_OK(mark(6));
+    HIP_OK(upsert_scan_hits(rp.hit, c->up_S.as<int32_t>(), DR, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(mark(7));
+    h_lb.resize(DR);
+    h_hit.resize(DR);
+    if (DR) {
+      HIP_OK(hipMemcpyAsync(h_lb.data(), rp.lb, (size_t)DR * 4, hipMemcpyDeviceToHost, c->stream));
+      HIP_OK(hipMemcpyAsync(h_hit.data(), rp.hit, (size_t)DR * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+  }
   float t_index = 0;
   // does a delta row need the int16 copy?  (known from the indexed descriptors)
   bool need_val2 = false;
@@ -3025,9 +3069,86 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   ap.reg_old = c->reg.as<RegRow>();
   ap.reg_delta = dreg;
   ap.reg_new = c->reg2.as<RegRow>();
-  HIP_OK(append_scan(ap, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
-  HIP_OK(launch_append(ap, c->stream));
-  HIP_OK(launch_append_recede(ap, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
+  int64_t n_sus = 0;
+  uint32_t sus_cnt[16] = {};
+  float t_sus = 0;
+  if (!upsert) {
+    HIP_OK(append_scan(ap, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(launch_append(ap, c->stream));
+    HIP_OK(launch_append_recede(ap, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
+  } else {
+    // what the ranks say, for the touched series only: the rows replaced, their dead bytes, the new
+    // series_row_ptr, and the suspects -- kept resident rows that carry ROW_UNSORTED and lie after
+    // their series' earliest replaced row, which may have been the flag's cause (as positions in the
+    // gathered array: a kept resident row k sits k + #delta rows inserted before it into its series)
+    std::vector<int64_t> sus;
+    for (int64_t i = 0; i < N2; i++) {
+      const int64_t p = ent[i].x, e0 = ent[i].z, en = ent[i].w;
+      const int64_t r0 = p >= 0 ? c->h_srp[p] : 0, res = p >= 0 ? c->h_srp[p + 1] - r0 : 0;
+      int64_t hits = 0;
+      for (int64_t k = e0; k < e0 + en; k++) hits += h_hit[k];
+      n_srp[i + 1] = n_srp[i] + res + en - hits;
+      if (!hits) continue;
+      n_repl += hits;
+      int64_t b = e0, ins = 0;   // the next delta row not before resident row k; inserted rows so far
+      bool after_replaced = false;
+      for (int64_t k = 0; k < res; k++) {
+        for (; b < e0 + en && h_lb[b] <= k && !h_hit[b]; b++) ins++;
+        if (b < e0 + en && h_lb[b] == k) {   // (a hit) resident row k is replaced
+          dead_q += align16(c->h_qlen[r0 + k]);
+          dead_v += align16(c->h_vlen[r0 + k]);
+          after_replaced = true;
+          b++;
+        } else if (after_replaced && (c->h_flags[r0 + k] & ROW_UNSORTED)) {
+          sus.push_back(n_srp[i] + k + ins);
+        }
+      }
+    }
+    NR2 = n_srp[N2];
+    if (NR2 != NR + DR - n_repl) return fail(TSDB_E_HIP, "tsdbhip_upsert: row count mismatch (internal)");
+    n_sus = (int64_t)sus.size();
+    UpsertParams up{};
+    up.ent = ap.ent;
+    up.srp_old = ap.srp_old;
+    up.rows_old = ap.rows_old;
+    up.rows_delta = drows;
+    up.lb = c->up_lb.as<int32_t>();
+    up.S = c->up_S.as<int32_t>();
+    up.n_series = N2;
+    up.n_rows = NR2;
+    up.srp_new = ap.srp_new;
+    up.rows_new = ap.rows_new;
+    up.gid_new = ap.gid_new;
+    up.reg_old = ap.reg_old;
+    up.reg_delta = dreg;
+    up.reg_new = ap.reg_new;
+    HIP_OK(mark(8));
+    HIP_OK(upsert_scan(up, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(launch_upsert(up, c->stream));
+    HIP_OK(mark(9));
+    if (n_sus) {   // indexed again exactly as tsdbhip_trim indexes its suspects, before the walk
+      HIP_OK(c->tr_list.ensure((size_t)n_sus * 8));
+      HIP_OK(c->tr_rows.ensure((size_t)n_sus * sizeof(RowDesc)));
+      HIP_OK(c->tr_reg.ensure((size_t)n_sus * sizeof(RegRow)));
+      HIP_OK(c->hint.ensure(std::max<int64_t>(DR, n_sus)));
+      HIP_OK(c->ilist.ensure(std::max<int64_t>(DR, n_sus) * 4));
+      HIP_OK(hipMemcpyAsync(c->tr_list.p, sus.data(), (size_t)n_sus * 8, hipMemcpyHostToDevice, c->stream));
+      RowDesc* const srows = c->tr_rows.as<RowDesc>();
+      RegRow* const sreg = c->tr_reg.as<RegRow>();
+      HIP_OK(launch_trim_stage(up.rows_new, c->tr_list.as<int64_t>(), n_sus, srows, c->stream));
+      const IndexBufs sib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
+      IndexClasses sik{};
+      HIP_OK(hipEventRecord(ev[2], c->stream));
+      const int rc = index_pass(srows, sreg, n_sus, sib, sik, sus_cnt);
+      if (rc) return rc;
+      HIP_OK(hipEventRecord(ev[3], c->stream));
+      HIP_OK(launch_trim_unstage(srows, sreg, c->tr_list.as<int64_t>(), n_sus, up.rows_new, up.reg_new, c->stream));
+      HIP_OK(hipStreamSynchronize(c->stream));   // (sus is pageable; the pass's time)
+      (void)hipEventElapsedTime(&t_sus, ev[2], ev[3]);
+    }
+    HIP_OK(mark(10));
+    HIP_OK(launch_trim_recede(up.rows_new, up.reg_new, up.srp_new, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
+  }
   HIP_OK(mark(4));
   if (NR2)
     HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
@@ -3039,8 +3160,21 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   if (tr.on) {
     float t[5] = {};
     for (int i = 0; i < 5; i++) (void)hipEventElapsedTime(&t[i], tr.e[i], tr.e[i + 1]);
-    std::fprintf(stderr, "[trace append] grow_copy %.3f upload %.3f index %.3f scan_gather %.3f desc_download %.3f ms\n",
-                 t[0], t[1], t[2], t[3], t[4]);
+    if (!upsert) {
+      std::fprintf(stderr, "[trace append] grow_copy %.3f upload %.3f index %.3f scan_gather %.3f desc_download %.3f ms\n",
+                   t[0], t[1], t[2], t[3], t[4]);
+    } else {   // (rank_download: the ranks' way to the host and the host's pass over them)
+      float rank = 0, scan = 0, dl = 0, gather = 0, sus = 0, recede = 0;
+      (void)hipEventElapsedTime(&rank, tr.e[2], tr.e[6]);
+      (void)hipEventElapsedTime(&scan, tr.e[6], tr.e[7]);
+      (void)hipEventElapsedTime(&dl, tr.e[7], tr.e[8]);
+      (void)hipEventElapsedTime(&gather, tr.e[8], tr.e[9]);
+      (void)hipEventElapsedTime(&sus, tr.e[9], tr.e[10]);
+      (void)hipEventElapsedTime(&recede, tr.e[10], tr.e[4]);
+      std::fprintf(stderr, "[trace upsert] grow_copy %.3f upload %.3f index_rank %.3f (delta_index %.3f) hit_scan %.3f rank_download %.3f "
+                           "scan_gather %.3f suspects %.3f (suspect_index %.3f) recede %.3f desc_download %.3f ms\n",
+                   t[0], t[1], rank, t_index, scan, dl, gather, sus, t_sus, recede, t[4]);
+    }
   }
   {
     const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
@@ -3107,9 +3241,10 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
     }
     c->cmp_errs.swap(kept);
   }
+  for (int k = 0; k < 16; k++) idx_cnt[k] += sus_cnt[k];   // (this call's index passes: the delta's plus the suspects')
   std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
   c->idx_fused = fused;
-  c->index_ms = t_index;
+  c->index_ms = t_index + t_sus;
   // what a load invalidates of the state that depends on the rows, the series' order or groups
   c->none_tiles_ready = false;
   c->acct_valid = false;
@@ -3123,9 +3258,49 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the batch they came from)
   c->pg.cells = 0;
   c->pg.qual_bytes = c->pg.value_bytes = 0;
-  const int rc = finish_classes(c);
-  fill_info(K, DR - n_repl, n_repl, grow_q || grow_v);
-  return rc;
+  mi->series_added = K;
+  mi->rows_added = DR - n_repl;
+  mi->rows_replaced = n_repl;
+  mi->rows_reindexed = n_sus;
+  mi->grew = grow_q || grow_v;
+  return finish_classes(c);
+}
+
+extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index,
+                              const uint8_t* series_new, tsdbhip_append_info* info) {
+  if (!c || !delta) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_append");
+  MergeInfo mi;
+  const int rc = merge_delta(c, delta, series_index, series_new, false, &mi);
+  if (rc || !info) return rc;
+  info->series_added = mi.series_added;
+  info->rows_added = mi.rows_added;
+  info->rows_replaced = mi.rows_replaced;
+  info->qual_capacity = c->qual.n;
+  info->val_capacity = c->val.n;
+  info->qual_dead = c->qual_dead;
+  info->val_dead = c->val_dead;
+  info->grew = mi.grew ? 1 : 0;
+  return 0;
+}
+
+extern "C" int tsdbhip_upsert(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index,
+                              const uint8_t* series_new, tsdbhip_upsert_info* info) {
+  if (!c || !delta) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_upsert");
+  MergeInfo mi;
+  const int rc = merge_delta(c, delta, series_index, series_new, true, &mi);
+  if (rc || !info) return rc;
+  info->series_added = mi.series_added;
+  info->rows_added = mi.rows_added;
+  info->rows_replaced = mi.rows_replaced;
+  info->rows_reindexed = mi.rows_reindexed;
+  info->qual_capacity = c->qual.n;
+  info->val_capacity = c->val.n;
+  info->qual_dead = c->qual_dead;
+  info->val_dead = c->val_dead;
+  info->grew = mi.grew ? 1 : 0;
+  return 0;
 }
 
 // Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead

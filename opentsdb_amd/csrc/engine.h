@@ -554,6 +554,38 @@ hipError_t launch_append(const AppendParams& p, hipStream_t s);
 // k_recede over the series at new positions touched[0 .. n): ROW_UNSORTED on delta rows only
 hipError_t launch_append_recede(const AppendParams& p, const int32_t* touched, int64_t n, const uint8_t* qual,
                                 hipStream_t s);
+// tsdbhip_upsert (k_upsert.hip): the resident RowDescs merged with a delta's by (series, base
+// time).  The delta's descriptors are in staging order: series by series, each series' rows by
+// base time.  Entry i of `ent` is the series at new position i, as AppendParams has it, with w =
+// its plain delta row count (which rows replace resident ones is found on the device).
+struct UpsertRankParams {
+  const int32_t* dser;        // [n_delta] the row's series: its current resident position (-1: a new series)
+  const int64_t* srp_old;     // [n_series_old + 1]
+  const RowDesc* rows_old;    // [n_rows_old]
+  const RowDesc* rows_delta;  // [n_delta] (only .base is read)
+  int64_t n_delta;
+  int32_t* lb;                // [n_delta] (out) lower bound of the row's base among its series' resident rows
+  int32_t* hit;               // [n_delta + 1] (out) 1: that base is resident, the row replaces it; [n_delta] = 0
+};
+struct UpsertParams {
+  const int4* ent;            // [n_series]
+  const int64_t* srp_old;     // [n_series_old + 1]
+  const RowDesc* rows_old;    // [n_rows_old]
+  const RowDesc* rows_delta;  // [n_delta] the delta's descriptors after their index pass
+  const int32_t* lb;          // [n_delta]
+  const int32_t* S;           // [n_delta + 1] exclusive scan of hit
+  int64_t n_series, n_rows;   // counts AFTER the upsert (the excluded tail included)
+  int64_t* srp_new;           // [n_series + 1]
+  RowDesc* rows_new;          // [n_rows]
+  int32_t* gid_new;           // [n_series]
+  const RegRow* reg_old;      // [n_rows_old]
+  const RegRow* reg_delta;    // [n_delta]
+  RegRow* reg_new;            // [n_rows]
+};
+hipError_t launch_upsert_rank(const UpsertRankParams& p, hipStream_t s);
+hipError_t upsert_scan_hits(const int32_t* hit, int32_t* S, int64_t n_delta, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t upsert_scan(const UpsertParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_upsert(const UpsertParams& p, hipStream_t s);
 // tsdbhip_trim (k_trim.hip): every loaded series without the first skip[i] of its rows; the
 // series' order and groups stay.
 struct TrimParams {

@@ -36,7 +36,7 @@ EXPORTS = [
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
-    "tsdbhip_debug_loaded",
+    "tsdbhip_debug_loaded", "tsdbhip_upsert",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -120,7 +120,8 @@ def lib():
         L.tsdbhip_load.argtypes = [vp, C.POINTER(abi.Batch)]
         L.tsdbhip_regroup.argtypes = [vp, C.c_void_p, C.c_int64]
         L.tsdbhip_append.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.AppendInfo)]
-        L.tsdbhip_trim.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
+        L.tsdbhip_upsert.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.UpsertInfo)]
+        L.tsdbhip_trim.argtypes =[vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
         L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
@@ -397,6 +398,20 @@ class Engine:
         info = abi.AppendInfo()
         # (an empty array's data pointer may be null: the library wants non-null pointers only with series)
         _check(lib().tsdbhip_append(self.ctx, C.byref(delta.c), idx.ctypes.data if len(idx) else None,
+                                    new.ctypes.data if len(new) else None, C.byref(info)))
+        return info
+
+    def upsert(self, delta: abi.HostBatch, series_index, series_new) -> abi.UpsertInfo:
+        """tsdbhip_upsert: the delta's rows upserted by (series, base time) anywhere in the resident
+        batch -- a row with the base time of any resident row of its series replaces it, every
+        other row is inserted where base order puts it.  series_index and series_new as for
+        append."""
+        idx = np.ascontiguousarray(series_index, dtype=np.int64)
+        new = np.ascontiguousarray(np.asarray(series_new) != 0, dtype=np.uint8)
+        if idx.ndim != 1 or idx.shape != new.shape or len(idx) != delta.n_series:
+            raise ValueError("series_index and series_new need one entry a delta series")
+        info = abi.UpsertInfo()
+        _check(lib().tsdbhip_upsert(self.ctx, C.byref(delta.c), idx.ctypes.data if len(idx) else None,
                                     new.ctypes.data if len(new) else None, C.byref(info)))
         return info
 

@@ -631,6 +631,44 @@ class ResidentSpans:
         self.scan_end_s = scan_end_s
         return info
 
+    def refresh(self, from_s: int, to_s: int | None = None):
+        """Bring rows the store has changed inside the resident range up to date without a reload
+        (Engine.upsert, tsdbhip_upsert): rescan [from_s, to_s) -- to_s defaults to the range's end
+        -- and hand the engine that delta.  A rescanned row replaces the resident row of the same
+        base time wherever it sits in its series (late datapoints, a compacted or repaired row),
+        any other is inserted by base time (a back-filled gap); series the scan meets for the
+        first time are inserted as extend inserts them.  The resident range does not move.  An
+        upsert cannot remove rows: a resident row inside the window that the rescan no longer
+        returns needs a reload.  Returns the engine's abi.UpsertInfo."""
+        if to_s is None:
+            to_s = self.scan_end_s
+        if from_s < self.scan_start_s or to_s > self.scan_end_s or to_s <= from_s:
+            raise ValueError(f"the window [{from_s}, {to_s}) is empty or outside the resident range "
+                             f"[{self.scan_start_s}, {self.scan_end_s})")
+        delta = self.store.scan(self.metric, from_s, to_s)
+        drows = dict(delta)
+        for sk, rows in self.spans:
+            got = {r[0] for r in drows.get(sk, [])}
+            for r in rows:
+                if from_s <= r[0] < to_s and r[0] not in got:
+                    raise ValueError(f"the resident row of base time {r[0]} is gone from the store: an upsert cannot "
+                                     "remove rows, reload the resident spans")
+        old = dict(zip(self.span_keys, self.spans))
+        # SpanCmp order over the union of the keys: the store's own series order (as extend)
+        merged_keys = [sk for sk in self.store.series(self.metric) if sk in old or sk in drows]
+        index_of = {sk: i for i, sk in enumerate(merged_keys)}
+        series_index = [index_of[sk] for sk, _ in delta]
+        series_new = [sk not in old for sk, _ in delta]
+        info = self.engine.upsert(make_batch(delta, [abi.GROUP_EXCLUDED] * len(delta)), series_index, series_new)
+        spans = []
+        for sk in merged_keys:
+            by_base = {r[0]: r for r in (old[sk][1] if sk in old else [])}
+            by_base.update({r[0]: r for r in drows.get(sk, [])})   # the delta wins
+            spans.append((sk, [by_base[b] for b in sorted(by_base)]))
+        self.spans = spans
+        self.span_keys = merged_keys
+        return info
+
     def trim(self, scan_start_s: int, pack_dead_pct: int = 50):
         """Move the resident range's start to scan_start_s without a reload (Engine.trim,
         tsdbhip_trim): the rows a scan of [scan_start_s, scan_end_s) no longer returns -- those
