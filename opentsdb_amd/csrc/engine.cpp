@@ -494,6 +494,7 @@ struct tsdbhip_ctx {
   int reg_cls = 0;                                     // ... bit cls: that class's regular list went through it
   bool fast_used = false;
   HostBuf h_stage;   // collect(): the dense [G][K] values and flags, page-locked
+  int64_t stage_err_gk = -1;   // collect() ended in a device error and left G * K values and flags of that run in h_stage (-1: not)
   HostBuf h_small;   // collect(): the group activity flags, error code and hand-back count, page-locked
   HostBuf h_scal;    // d2h_small: 16 page-locked 8-byte slots for scalars read back
   void* small_dst[16] = {};
@@ -5565,6 +5566,7 @@ int collect(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G, bo
   const int32_t err = *sm.err, redo_n = *sm.redo;
   tr.mark("device + d2h");
   if (timed) record_timing(c, P, redo_n);
+  c->stage_err_gk = err ? gk : -1;
   if (err) return fail(err, "error raised by the device path");
   if (P.mode == MODE_ALL) {
     // AggregationIterator ctor: the single "all" point is skipped unless start_time <= qs <= end_time
@@ -6499,12 +6501,81 @@ int run_multi_fused(tsdbhip_ctx* c, const tsdbhip_query* qs, int n, tsdbhip_resu
 
 }  // namespace
 
+namespace {
+
+int run_single(tsdbhip_ctx* c, const tsdbhip_query* q, tsdbhip_result** out, bool timed = true);
+
+// Which exception a FILL_SCALAR query raises when one group meets a missing bucket
+// (FillingDownsampler.next: RuntimeException) and another an infinite value
+// (AggregationIterator: IllegalStateException).  The reference iterates the groups in order, so
+// the group that comes first decides; the device error word keeps the first code any kernel sets
+// and carries no group.  On this error path only: the infinite values are read from the dense
+// output the failed run left in the staging buffer, and the series with a missing bucket from a
+// count downsampling of the same grid under FILL_NAN, one result a series (a present bucket counts
+// its non-NaN values, a missing one is NaN).  A group that holds both keeps the run's own code.
+int scalar_fill_error(tsdbhip_ctx* c, const tsdbhip_query* q, int rc) {
+  if (q->ds_fill != TSDB_FILL_SCALAR || (rc != TSDB_E_RUNTIME && rc != TSDB_E_ILLEGAL_STATE) || c->ro_active) return rc;
+  Plan P;
+  if (plan_query(c, q, P) || P.raw || P.anchored || P.mode != MODE_GRID || P.K <= 0) return rc;
+  const int64_t G = P.none ? c->n_series : c->n_groups, K = P.K;
+  if (c->stage_err_gk != G * K) return rc;
+  const int64_t NO = INT64_MAX;
+  int64_t g_inf = NO, g_gap = NO;
+  {
+    const double* val = reinterpret_cast<const double*>(c->h_stage.p);
+    const uint8_t* flag = reinterpret_cast<const uint8_t*>(c->h_stage.p) + G * K * 8;
+    for (int64_t g = 0; g < G; g++)
+      for (int64_t k = 0; k < K; k++)
+        if (flag[g * K + k] && std::isinf(val[g * K + k])) { g_inf = std::min(g_inf, P.none ? c->h_orig[g] : g); break; }
+  }
+  tsdbhip_query q2 = *q;
+  q2.aggregator = TSDB_AGG_NONE;
+  q2.ds_function = TSDB_AGG_COUNT;
+  q2.ds_fill = TSDB_FILL_NAN;
+  q2.rate = 0;
+  q2.flags = 0;
+  Plan P2;
+  if (plan_query(c, &q2, P2) || P2.mode != MODE_GRID || P2.K != K || P2.B0 != P.B0) return rc;
+  tsdbhip_result* tmp = nullptr;
+  const int rc2 = run_single(c, &q2, &tmp, false);
+  result_free(tmp);
+  if (rc2) return fail(rc, "error raised by the device path");
+  const int64_t S = c->n_series;
+  const bool lead = P.B0 > P.ss * 1000;   // the grid's bucket before slot 0 is always missing
+  const double* val = reinterpret_cast<const double*>(c->h_stage.p);
+  const uint8_t* flag = reinterpret_cast<const uint8_t*>(c->h_stage.p) + S * K * 8;
+  for (int64_t s = 0; s < S; s++) {
+    if (!P.none && !(c->h_group[s] >= 0 && c->h_group[s] < c->n_groups)) continue;
+    bool in_range = false, gap = false;
+    for (int64_t k = 0; k < K; k++) {
+      if (!flag[s * K + k]) continue;
+      in_range = true;
+      gap = gap || std::isnan(val[s * K + k]);
+    }
+    if (in_range && (gap || lead)) g_gap = std::min(g_gap, P.none ? c->h_orig[s] : (int64_t)c->h_group[s]);
+  }
+  if (g_inf == NO && g_gap == NO) return fail(rc, "error raised by the device path");
+  if (g_inf == g_gap) return fail(rc, "error raised by the device path");
+  return g_inf < g_gap ? fail(TSDB_E_ILLEGAL_STATE, "Got Infinity (error raised by the device path)")
+                       : fail(TSDB_E_RUNTIME, "unhandled fill policy (error raised by the device path)");
+}
+
+}  // namespace
+
 extern "C" int tsdbhip_run(tsdbhip_ctx* c, const tsdbhip_query* q, tsdbhip_result** out) {
   if (c && c->md) return tsdb::md_run(c, q, out);
   if (!c || !q || !out) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
   CtxLock lk(c);
   *out = nullptr;
   HIP_OK(hipSetDevice(c->device));
+  c->stage_err_gk = -1;
+  const int rc = run_single(c, q, out);
+  return rc ? scalar_fill_error(c, q, rc) : 0;
+}
+
+namespace {
+
+int run_single(tsdbhip_ctx* c, const tsdbhip_query* q, tsdbhip_result** out, bool timed) {
   if (c->ro_active) return run_rollup(c, q, out);
   Plan P;
   int rc = plan_query(c, q, P);
@@ -6515,13 +6586,15 @@ extern "C" int tsdbhip_run(tsdbhip_ctx* c, const tsdbhip_query* q, tsdbhip_resul
   if (P.gsel || P.ordered) {
     rc = P.gsel ? run_sel_group(c, q, P, G) : run_ordered(c, q, P, G);
     if (rc) return rc;
-    return collect(c, q, P, G, true, out);
+    return collect(c, q, P, G, timed, out);
   }
   P.seq_dense = seq_dense_wanted(c, P);
   rc = run_device(c, q, P, G, true);
   if (rc) return rc;
-  return collect(c, q, P, G, true, out);
+  return collect(c, q, P, G, timed, out);
 }
+
+}  // namespace
 
 // Several group-by aggregators over one downsampling (a TSQuery with several sub-queries over
 // one metric).  With a percentile / median downsampling function one bucket-selection pass

@@ -1050,6 +1050,12 @@ __device__ __forceinline__ void emit_series_to(const GridParams& p, const WaveLd
     int prev_item = -1, last_surv = -1;
     long long nsurv = 0;
     const bool dense_stream = p.fill != TSDB_FILL_NONE && p.mode != MODE_ALL;
+    // An interval that does not divide the scan start: FillingDownsampler's grid starts one bucket
+    // before slot 0 (:113-135), and the seek has left that bucket empty.  Its fill value is the
+    // previous point of slot 0's rate; AggregationIterator drops its own rate with the point
+    // (before start_time, ctor :424-441).  (MODE_TABLE carries such a bucket as slot 0: skip0.)
+    const bool lead = dense_stream && p.mode == MODE_GRID && p.B0 > p.ss * 1000;
+    if (lead && p.fill == TSDB_FILL_SCALAR) set_err(p.err, TSDB_E_RUNTIME);
     for (int kb = 0; kb < K; kb += 64) {
       const int k = kb + lane;
       const bool inK = k < K;
@@ -1067,6 +1073,7 @@ __device__ __forceinline__ void emit_series_to(const GridParams& p, const WaveLd
         double v0 = 0.0;
         long long t0 = 0;
         if (pi >= 0) { v0 = W.pres[pi] ? W.dense[pi] : fillv; t0 = p.B0 + slot_rel(p, pi); }
+        else if (lead) { v0 = fillv; t0 = p.B0 - p.I; }
         const long long t1 = (p.mode == MODE_ALL) ? p.qs : p.B0 + slot_rel(p, k);
         if (t1 <= t0) set_err(p.err, TSDB_E_ILLEGAL_STATE);
         const double dt = (double)(t1 - t0) / 1000.0;
