@@ -17,7 +17,7 @@
 #define SHORT6_VL4 0   // 4: the float32 class takes 6 a lane too (measured no faster: profiles/r04ab)
 #endif
 #ifndef FAST_REG_D4
-#define FAST_REG_D4 4  // k_fast REG ring depth, 4-byte values (16 B a lane a slot)
+#define FAST_REG_D4 3  // k_fast REG ring depth, 4-byte values (16 B a lane a slot; KR 1: 75 VGPRs, 6 waves a SIMD)
 #endif
 #ifndef FAST_REG_D8
 #define FAST_REG_D8 3  // k_fast REG ring depth, 8-byte values (32 B a lane a slot)

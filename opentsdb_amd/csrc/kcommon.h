@@ -1699,14 +1699,14 @@ __device__ __forceinline__ bool fast_row_ok(uint32_t flags, bool minmax, bool ce
 struct FDesc {       // the descriptor fields the walker needs
   uint64_t qoff, voff;
   uint32_t base, ndp, flags;
-  uint32_t first, step;   // REG: the row's RegRow entry
+  uint32_t fs;            // REG: the row's RegRow entry, first | step << 16 (offsets of 2-byte qualifiers are < 4096)
 };
 
 __device__ __forceinline__ FDesc fdesc(const RowDesc* __restrict__ rows, int64_t r) {
   const RowDesc& x = rows[r];
   FDesc d;
   d.qoff = x.qoff; d.voff = x.voff; d.base = x.base; d.ndp = x.ndp; d.flags = x.flags;
-  d.first = d.step = 0;
+  d.fs = 0;
   return d;
 }
 
@@ -1714,8 +1714,13 @@ template <bool REG>
 __device__ __forceinline__ FDesc fdesc_r(const GridParams& p, const RowDesc* __restrict__ rows, int64_t r) {
   FDesc d = fdesc(rows, r);
   if constexpr (REG) {
-    const RegRow g = p.reg[r];
-    d.first = g.first; d.step = g.step;
+    // The side array is read-only for the whole launch: read through the constant address space
+    // the entry comes with scalar loads beside the descriptor's.  (Through GridParams the
+    // compiler issued a vector load and waited for vmcnt(0) at every row, which drained the
+    // wave's ring of value loads.)
+    typedef const __attribute__((address_space(4))) RegRow* CReg;
+    const CReg g = (CReg)(p.reg + r);
+    d.fs = g->first | (g->step << 16);
   }
   return d;
 }
@@ -1748,7 +1753,7 @@ __device__ __forceinline__ int fast_issue(const GridParams& p, const RowDesc* __
       if ((int64_t)w.d.base < p.ss || (int64_t)w.d.base >= p.se) { fwalk_next_row<REG>(p, rows, w); continue; }
       if (!fast_row_ok<QW, VL>(w.d.flags, F == F_MIN || F == F_MAX, F == F_SUM || F == F_AVG)) return 2;
       if (VL == 0 && w.d.ndp > CH) return 2;
-      if (REG && w.d.step == 0) return 2;   // (not on a correct regular list)
+      if (REG && (w.d.fs >> 16) == 0) return 2;   // (not on a correct regular list)
     }
     if (w.c0 < (int64_t)w.d.ndp) break;
     fwalk_next_row<REG>(p, rows, w);
@@ -1761,8 +1766,8 @@ __device__ __forceinline__ int fast_issue(const GridParams& p, const RowDesc* __
   // lanes past the end of the row re-read its first datapoints (in bounds, ignored)
   const int64_t i0 = (lane * DPL < nv0) ? w.c0 + (int64_t)lane * DPL : 0;
   if constexpr (REG) {
-    m.f0 = w.d.first + (uint32_t)w.c0 * w.d.step;
-    m.step = w.d.step;
+    m.step = w.d.fs >> 16;
+    m.f0 = (w.d.fs & 0xFFFFu) + (uint32_t)w.c0 * m.step;
   } else {
     const uint4* q = reinterpret_cast<const uint4*>(p.qual + w.d.qoff + i0 * QW);
 #pragma unroll
@@ -1864,23 +1869,16 @@ __device__ __forceinline__ int f_slot(const GridParams& p, const FGeom& m, int n
   return m.q0 + (int)((double)n * p.rcpn);
 }
 
-// Folds one chunk into the series' slot accumulators.
-// REG: the offset fields are f0 + i * step (i: the datapoint's place in the chunk)
-template <int F, int QW, int VL, bool FULL, int NP = DPL, bool REG = false>
-__device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L, const FRaw<QW, VL, REG>& b,
-                                           const FGeom& m, int nv0, int K, uint32_t f0 = 0, uint32_t step = 0) {
+// Folds one chunk into the series' slot accumulators.  (Regular rows: fast_chunk_reg.)
+template <int F, int QW, int VL, bool FULL, int NP = DPL>
+__device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L, const FRaw<QW, VL>& b,
+                                           const FGeom& m, int nv0, int K) {
   const int lane = lane_id();
   const int nvl = FULL ? NP : max(0, min(NP, nv0 - lane * NP));
   const int uq = (QW == 2 && !p.unit_s) ? 1000 : 1;
   uint32_t fld[NP];
-  if constexpr (REG) {
-    const uint32_t fl0 = f0 + (uint32_t)(lane * NP) * step;
 #pragma unroll
-    for (int j = 0; j < NP; j++) fld[j] = fl0 + (uint32_t)j * step;
-  } else {
-#pragma unroll
-    for (int j = 0; j < NP; j++) fld[j] = f_field<QW, VL>(b, j);
-  }
+  for (int j = 0; j < NP; j++) fld[j] = f_field<QW, VL>(b, j);
   // vle integers (1-2 bytes): the in-lane runs are folded in int32 (8 values of |x| < 2^15
   // sum exactly) and converted once per run; squareSum stays in double
   constexpr bool IP = (VL == 0) && (F != F_SQUARESUM);
@@ -1979,6 +1977,97 @@ __device__ __forceinline__ void fast_chunk(const GridParams& p, const FastLds& L
         }
       }
     }
+  }
+}
+
+// The chunk fold of a regular row (REG): datapoint i of the chunk lies at n = nA + i * su
+// (nA = r0 + f0 * uq, su = step * uq, n-units from the start of slot q0), so the bucket geometry
+// is arithmetic and nothing is computed per datapoint but the sums:
+// - per chunk (scalar): the chunk lies inside the slot range when nA >= 0 and its last point is
+//   below (K - q0) * In; a lane's 8 points span at most two buckets when 7 * su <= In (n0 = a In + r
+//   with r < In gives n0 + 7 su < (a + 2) In; 7 su = In + 1 and r = In - 1 reach bucket a + 2).  A
+//   chunk that fails either test takes the per-datapoint loop of fast_chunk (same slots, same
+//   values; any split of a bucket's values adds to the same bits under the certificate, min / max
+//   are order-free);
+// - per lane: n0 = nA + lane * 8 su, one division by In (rcpn: exact for 0 <= n < 2^50), the
+//   distance Dn to the next bucket boundary and the first run's length cF = min(nvl, ceil(Dn / su)),
+//   which is the number of j < nvl with j * su < Dn -- the datapoints fast_chunk's compare of
+//   every offset field against Tf selects (fld * uq < Dn  <=>  fld < ceil(Dn / uq)).
+template <int F, int VL, bool FULL>
+__device__ __forceinline__ void fast_chunk_reg(const GridParams& p, const FastLds& L, const FRaw<2, VL, true>& b,
+                                               const FGeom& m, int nv0, int K, uint32_t f0, uint32_t step) {
+  constexpr int NP = DPL;
+  const int lane = lane_id();
+  const int uq = p.unit_s ? 1 : 1000;
+  const int su = (int)step * uq;                  // offset fields are < 4096: no overflow
+  const int nc = FULL ? CH : nv0;                 // the chunk's datapoints (FULL: nv0 >= CH)
+  const int nA = m.r0 + (int)f0 * uq;
+  const int nZ = nA + (nc - 1) * su;
+  const bool inside = nA >= 0 && (int64_t)nZ < (int64_t)(K - m.q0) * p.In;
+  if (__builtin_expect(!(inside && (NP - 1) * su <= p.In), 0)) {
+    // the edge of the slot range, or a lane over more than two buckets: per datapoint
+    const int nvl = FULL ? NP : max(0, min(NP, nv0 - lane * NP));
+    const int n0 = nA + lane * (NP * su);
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+      if (j < nvl) {
+        const int n = n0 + j * su;
+        if (n >= 0) {
+          const int s = f_slot(p, m, n);
+          if (s < K) {
+            double x = f_value<2, VL, true>(b, j);
+            if (F == F_SQUARESUM) x = x * x;
+            fast_fold<F>(L, s, x, 1u);
+          }
+        }
+      }
+    }
+    return;
+  }
+  const int nvl = FULL ? NP : max(0, min(NP, nv0 - lane * NP));
+  if (!FULL && nvl == 0) return;
+  const int n0 = nA + lane * (NP * su);
+  const int q = (int)((double)n0 * p.rcpn);       // n0 / In
+  const int Dn = (q + 1) * p.In - n0;             // n-units to the next bucket boundary: 0 < Dn <= In
+  int cF;
+  if (su == 1) {                                  // (uniform branch)
+    cF = min(nvl, Dn);
+  } else {
+    cF = 1;
+#pragma unroll
+    for (int j = 1; j < NP; j++) cF += (j * su < Dn) ? 1 : 0;
+    cF = min(nvl, cF);
+  }
+  const int sfirst = m.q0 + q;
+  const int nL = nvl - cF;
+  if constexpr (F == F_COUNT) {
+    fast_fold<F>(L, sfirst, 0.0, (uint32_t)cF);
+    if (nL > 0) fast_fold<F>(L, sfirst + 1, 0.0, (uint32_t)nL);
+  } else if constexpr (F == F_MIN || F == F_MAX) {
+    double sF = fast_identity<F>(), mL = fast_identity<F>();
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+      const double x = f_value<2, VL, true>(b, j);
+      const double a = j < cF ? x : fast_identity<F>();
+      const double c = (j >= cF && (FULL || j < nvl)) ? x : fast_identity<F>();
+      sF = F == F_MIN ? fmin(sF, a) : fmax(sF, a);
+      mL = F == F_MIN ? fmin(mL, c) : fmax(mL, c);
+    }
+    fast_fold<F>(L, sfirst, sF, (uint32_t)cF);
+    if (nL > 0) fast_fold<F>(L, sfirst + 1, mL, (uint32_t)nL);
+  } else {
+    // P: the lane's sum; sF: the sum of the first cF (a prefix of the same chain, as fast_chunk)
+    double P = 0.0, sF = 0.0;
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+      double x = f_value<2, VL, true>(b, j);
+      if (F == F_SQUARESUM) x = x * x;
+      if (!FULL && j >= nvl) x = 0.0;
+      P += x;
+      if (j == 0 || j < cF) sF = P;
+    }
+    fast_fold<F>(L, sfirst, sF, (uint32_t)cF);
+    if (nL > 0) fast_fold<F>(L, sfirst + 1, P - sF, (uint32_t)nL);   // exact (certificate)
   }
 }
 
@@ -2256,8 +2345,13 @@ __global__ __launch_bounds__(256) void k_fast(GridParams p, const RowDesc* __res
           if (p.oneb && fast_chunk_oneb<F, QW, VL>(p, L, buf[i], g, nv0, K, rf0, rstep)) {
           } else
 #endif
-          if (nv0 >= CH) fast_chunk<F, QW, VL, true>(p, L, buf[i], g, nv0, K, rf0, rstep);
-          else fast_chunk<F, QW, VL, false>(p, L, buf[i], g, nv0, K, rf0, rstep);
+          if constexpr (REG) {
+            if (nv0 >= CH) fast_chunk_reg<F, VL, true>(p, L, buf[i], g, nv0, K, rf0, rstep);
+            else fast_chunk_reg<F, VL, false>(p, L, buf[i], g, nv0, K, rf0, rstep);
+          } else {
+            if (nv0 >= CH) fast_chunk<F, QW, VL, true>(p, L, buf[i], g, nv0, K);
+            else fast_chunk<F, QW, VL, false>(p, L, buf[i], g, nv0, K);
+          }
           if (fast_issue<F, QW, VL, REG>(p, rows, w, buf[i], meta[i]) == 2) { redo = true; done = true; }
         }
       }
