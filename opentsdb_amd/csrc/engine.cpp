@@ -448,7 +448,11 @@ struct tsdbhip_ctx {
   int64_t n_grouped = -1;              // series before the first ungrouped one, when every later one
                                        // is ungrouped (else n_series); -1 = not computed
   DevBuf big_scratch;                  // k_pct large buckets: per-wave overflow regions
-  bool mdp_valid = false;              // series_max_dp() cache (invalidated by every load)
+  // the validity flags of what is derived from the resident batch -- none_tiles_ready, row_ser_valid
+  // and n_grouped above, the five below, acct_valid and seqd_valid further down -- are cleared by
+  // every load and every edit of the batch in one place, invalidate_caches(): a new cache's flag
+  // goes there and nowhere else
+  bool mdp_valid = false;              // series_max_dp() cache
   bool ro_meta_valid = false;          // rollup ro_ord / ro_orig / ro_allint of the loaded batch
   bool lc_valid = false;               // local_counts() cache
   std::vector<int64_t> lc;
@@ -511,7 +515,7 @@ struct tsdbhip_ctx {
   bool idx_fused = false;                // the last load's short rows were indexed by the classifying pass
   double compact_ms = 0;                 // k_compact pipeline of the last tsdbhip_load_cells
   int64_t fused_n = 0;                   // queries of the fused multi-aggregator pass being collected
-  // account() cache (invalidated by every load)
+  // account() cache (invalidate_caches)
   bool acct_valid = false;
   bool seqd_valid = false;             // cached seq_dense_wanted answer for (seqd_ss, seqd_se)
   bool seqd_uniform = false;          // every row of the cached scan range has one qualifier width and value length
@@ -838,6 +842,30 @@ extern "C" int tsdbhip_init(int device, tsdbhip_ctx** out) {
   return 0;
 }
 
+// What a load or an edit of the resident batch (tsdbhip_regroup / _append / _upsert / _trim)
+// invalidates of the state derived from its rows, the series' order or the groups.  The one place
+// a new cache is cleared.
+static void invalidate_caches(tsdbhip_ctx* c) {
+  c->none_tiles_ready = false;
+  c->acct_valid = false;
+  c->seqd_valid = false;
+  c->row_ser_valid = false;
+  c->n_grouped = -1;
+  c->mdp_valid = false;
+  c->ro_meta_valid = false;
+  c->lc_valid = false;
+  c->calc_valid = false;
+  c->pg.cells = 0;   // (the pre-aggregate cells belong to the batch they came from)
+  c->pg.qual_bytes = c->pg.value_bytes = 0;
+}
+// ... and, for an edit, the rollup cells of the last tsdbhip_rollup_run, which belong to the batch
+// as it was.  (release_batch leaves ro_n alone: the cells live in ro_out, buffers of their own that
+// a load does not release, and stay downloadable after it, as they always have.)
+static void invalidate_derived(tsdbhip_ctx* c) {
+  invalidate_caches(c);
+  c->ro_n = 0;
+}
+
 static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
@@ -848,15 +876,7 @@ static void release_batch(tsdbhip_ctx* c) {
   c->n_series_loaded = c->n_rows_loaded = 0;
   c->regroup_ok = false;
   c->h_excl.clear();
-  c->none_tiles_ready = false;
-  c->acct_valid = false;
-  c->seqd_valid = false;
-  c->row_ser_valid = false;
-  c->n_grouped = -1;
-  c->mdp_valid = false;
-  c->ro_meta_valid = false;
-  c->lc_valid = false;
-  c->calc_valid = false;
+  invalidate_caches(c);
   c->n_series = c->n_rows = c->n_groups = 0;
   c->max_series_rows = INT64_MAX;   // (unknown until a load sets it: k_recede runs)
   c->ro_active = c->ro_counts = false;
@@ -876,8 +896,6 @@ static void release_batch(tsdbhip_ctx* c) {
   c->ro_nruns = 0;
   c->cmp_errs.clear();
   c->compact_ms = 0;
-  c->pg.cells = 0;   // (the pre-aggregate cells belong to the batch they came from)
-  c->pg.qual_bytes = c->pg.value_bytes = 0;
 }
 
 namespace tsdb {
@@ -1105,7 +1123,28 @@ static int finish_classes(tsdbhip_ctx* c) {
   return build_tiles(c);
 }
 
-static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
+// does an indexed row read the int16 copy of its values (val2)?  2-byte qualifiers, 1-2-byte integers
+static bool row_wants_val2(uint32_t flags) {
+  return (flags & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2);
+}
+// does a val2 of v2_bytes, allocated up front for index_fused, fit with room to spare?
+static bool fused_index_fits(size_t v2_bytes) {
+  size_t fr = 0, tot = 0;
+  return hipMemGetInfo(&fr, &tot) == hipSuccess && fr > v2_bytes + ((size_t)8 << 30);
+}
+// the per-row host mirrors, sized by the caller, from n downloaded descriptors
+static void split_rows(const RowDesc* d, int64_t n, std::vector<uint32_t>& base, std::vector<uint32_t>& ndp,
+                       std::vector<uint32_t>& qlen, std::vector<uint32_t>& vlen, std::vector<uint32_t>& flags) {
+  for (int64_t r = 0; r < n; r++) {
+    base[r] = d[r].base;
+    ndp[r] = d[r].ndp;
+    qlen[r] = d[r].qlen;
+    vlen[r] = d[r].vlen;
+    flags[r] = d[r].flags;
+  }
+}
+
+static int finish_load(tsdbhip_ctx* c) {
   // classify rows on the device, then fetch ndp for host-side accounting
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
   const bool generic = opt_is(OPT_INDEX_GENERIC, 1);   // test hook: sequential per-datapoint path
@@ -1123,9 +1162,7 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   // classes first, val2 only when some row can need it (a 216-GB store has no room for a spare 72)
   bool fused = false;
   if (!generic) {
-    size_t fr = 0, tot = 0;
-    if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess &&
-        fr > c->qual_bytes + BLOB_SLACK + ((size_t)8 << 30)) {
+    if (!opt_off(OPT_INDEX_FUSED) && fused_index_fits(c->qual_bytes + BLOB_SLACK)) {
       HIP_OK(c->val2.ensure(c->qual_bytes + BLOB_SLACK));
       fused = true;
     }
@@ -1168,7 +1205,7 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
   t_index += t_cls;
   bool need_val2 = false;
   for (const RowDesc& d : back)
-    if ((d.flags & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2)) { need_val2 = true; break; }
+    if (row_wants_val2(d.flags)) { need_val2 = true; break; }
   if (!need_val2) {
     c->val2.release();
   } else if (generic) {   // test hook: the sequential path writes the copy in a second pass
@@ -1183,19 +1220,8 @@ static int finish_load(tsdbhip_ctx* c, const std::vector<RowDesc>& rd) {
     (void)hipEventElapsedTime(&t_val2, c->ev[2], c->ev[3]);
   }
   c->index_ms = (double)t_index + t_val2;
-  (void)rd;
-  c->h_ndp.resize(c->n_rows);
-  c->h_base.resize(c->n_rows);
-  c->h_qlen.resize(c->n_rows);
-  c->h_vlen.resize(c->n_rows);
-  c->h_flags.resize(c->n_rows);
-  for (int64_t r = 0; r < c->n_rows; r++) {
-    c->h_ndp[r] = back[r].ndp;
-    c->h_base[r] = back[r].base;
-    c->h_qlen[r] = back[r].qlen;
-    c->h_vlen[r] = back[r].vlen;
-    c->h_flags[r] = back[r].flags;
-  }
+  for (auto* v : {&c->h_ndp, &c->h_base, &c->h_qlen, &c->h_vlen, &c->h_flags}) v->resize(c->n_rows);
+  split_rows(back.data(), c->n_rows, c->h_base, c->h_ndp, c->h_qlen, c->h_vlen, c->h_flags);
   c->n_series_loaded = c->n_series;
   c->n_rows_loaded = c->n_rows;
   // malformed rows are reported lazily, when a query reads them (as the reference does)
@@ -1258,18 +1284,39 @@ static bool merge_cells(std::vector<uint8_t>& lq, std::vector<uint8_t>& lv, cons
   return true;
 }
 
+// A batch's sizes and arrays, before anything reads them: what tsdbhip_load and a delta
+// (tsdbhip_append / tsdbhip_upsert) check alike.  own_missing: an array of the caller's own, one
+// entry a series, is null.  every_row: every series and row as well -- a load checks the series it
+// reads, and after it has released the old batch.
+static int check_batch(const tsdbhip_batch* b, bool own_missing, bool every_row) {
+  if (b->n_series < 0 || b->n_rows < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
+  if (b->n_series > 0 && (!b->series_row_ptr || !b->group_id || own_missing))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
+  if (b->n_rows > 0 && (!b->row_base_time || !b->row_qual_off || !b->row_val_off || !b->qual || !b->val))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
+  if (b->n_series > 0 && (b->series_row_ptr[0] != 0 || b->series_row_ptr[b->n_series] != b->n_rows))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr does not cover the rows");
+  if (!every_row) return 0;
+  for (int64_t s = 0; s < b->n_series; s++)
+    if (b->series_row_ptr[s + 1] < b->series_row_ptr[s]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr not monotonic");
+  for (int64_t r = 0; r < b->n_rows; r++) {
+    if (b->row_qual_off[r + 1] < b->row_qual_off[r] || b->row_val_off[r + 1] < b->row_val_off[r])
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row offsets not monotonic");
+    if (b->row_qual_off[r + 1] - b->row_qual_off[r] > 0xFFFFFFFFull || b->row_val_off[r + 1] - b->row_val_off[r] > 0xFFFFFFFFull)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
+  }
+  return 0;
+}
+
 // Loads series cand[0 .. m) of the batch (all series when cand is null), in that order as the
 // "batch order" of the resident store (NONE results are emitted in it); series are then stably
 // sorted by group (SpanGroup membership, order inside a group kept).
 // (the caller holds c->mu: tsdbhip_load_rollup sets its rollup state under the same lock)
 static int load_body(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<int64_t>* cand) {
   HIP_OK(hipSetDevice(c->device));
-  if (b->n_series < 0 || b->n_rows < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  if (b->n_series > 0 && (!b->series_row_ptr || !b->group_id)) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
-  if (b->n_rows > 0 && (!b->row_base_time || !b->row_qual_off || !b->row_val_off || !b->qual || !b->val))
-    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
-  if (b->n_series > 0 && (b->series_row_ptr[0] != 0 || b->series_row_ptr[b->n_series] != b->n_rows))
-    return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr does not cover the rows");
+  if (const int rc = check_batch(b, false, false)) return rc;
+  // (the per-series and per-row checks come after the release, as they always have: a load they
+  // refuse leaves no batch resident)
   release_batch(c);
   const int64_t m = cand ? (int64_t)cand->size() : b->n_series;
   auto ser = [&](int64_t v) { return cand ? (*cand)[v] : v; };   // virtual batch position -> batch series
@@ -1354,7 +1401,7 @@ static int load_body(tsdbhip_ctx* c, const tsdbhip_batch* b, const std::vector<i
   HIP_OK(h2d(c, c->val.p, hv.data(), hv.size(), c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
   if (c->n_series) HIP_OK(hipMemcpy(c->gid.p, c->h_group.data(), c->n_series * 4, hipMemcpyHostToDevice));
-  const int rc = finish_load(c, rd);
+  const int rc = finish_load(c);
   c->regroup_ok = rc == 0 && !cand;   // (a shard's group numbering is global: tsdbhip_regroup refuses it)
   return rc;
 }
@@ -2348,7 +2395,7 @@ extern "C" int tsdbhip_load_cells(tsdbhip_ctx* c, const tsdbhip_cell_batch* cb) 
   HIP_OK(hipMemcpy(c->srp.p, srp.data(), (NS + 1) * 8, hipMemcpyHostToDevice));
   if (NS) HIP_OK(hipMemcpy(c->gid.p, hgroup.data(), NS * 4, hipMemcpyHostToDevice));
   mark("write+merge");
-  const int rc = finish_load(c, rd);
+  const int rc = finish_load(c);
   mark("finish_load");
   c->cmp_errs = std::move(errs);
   c->compact_ms = cmp_ms;
@@ -2551,7 +2598,7 @@ static int synth_impl(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t p0, 
     for (int64_t i = std::max(grp_off[g], p0); i < std::min(grp_off[g + 1], p1); i++) c->h_group[i - p0] = (int32_t)g;
   std::iota(c->h_orig.begin(), c->h_orig.end(), 0);
   HIP_OK(hipStreamSynchronize(c->stream));
-  const int rc = finish_load(c, rd);
+  const int rc = finish_load(c);
   c->regroup_ok = rc == 0 && !shard;
   return rc;
 }
@@ -2564,6 +2611,224 @@ extern "C" int tsdbhip_synth(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp) {
 extern "C" int tsdbhip_synth_shard(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp, int64_t pos_begin, int64_t pos_end) {
   MD_REFUSE(c, "tsdbhip_synth_shard");
   return synth_impl(c, sp, pos_begin, pos_end, true);
+}
+
+// ===========================================================================
+// in-place edits of the resident batch: tsdbhip_regroup, tsdbhip_append, tsdbhip_upsert,
+// tsdbhip_trim.  One skeleton: validate, allocate, queue, download, commit,
+// invalidate_derived, finish_classes -- the resident batch stays as it is until the commit.
+// ===========================================================================
+
+// blobs an edit allocated and has not handed to the context
+struct BlobHold {
+  DevBuf q, v, v2;
+  ~BlobHold() { q.release(); v.release(); v2.release(); }
+};
+
+// an edit's blob allocation failed; hint: what did not fit
+static int edit_nomem(const std::string& fn, hipError_t e, const char* hint) {
+  (void)hipGetLastError();
+  return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, fn + ": " + hint) : fail(TSDB_E_HIP, fn + ": " + hipGetErrorString(e));
+}
+
+// the capacity of a blob allocated for `need` bytes: option APPEND_RESERVE per cent on top
+static size_t grown(uint64_t need) {
+  const int64_t reserve = opt(OPT_APPEND_RESERVE) < 0 ? 50 : opt(OPT_APPEND_RESERVE);
+  return (size_t)(need + need / 100 * reserve + need % 100 * reserve / 100);
+}
+
+// option TRACE: an edit's stages by hipEvents of the call's own (stream time between stage ends,
+// the host work in between included); the call prints them on stderr
+template <int N> struct StageTrace {
+  hipEvent_t e[N] = {};
+  hipStream_t s = nullptr;
+  bool on = false;
+  ~StageTrace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t begin(hipStream_t stream) {
+    s = stream;
+    on = opt_is(OPT_TRACE, 1);
+    hipError_t r = hipSuccess;
+    for (int i = 0; on && i < N && r == hipSuccess; i++) r = hipEventCreate(&e[i]);
+    return r;
+  }
+  hipError_t mark(int i) { return on ? hipEventRecord(e[i], s) : hipSuccess; }
+  float ms(int from, int to) const {
+    float t = 0;
+    (void)hipEventElapsedTime(&t, e[from], e[to]);
+    return t;
+  }
+};
+
+// The series of an edited batch in the order a fresh load would give them: stably sorted by
+// (key, batch index), keys being the group, G for an ungrouped series and G + 1 for an excluded
+// one.  A counting sort in two steps, so that each caller keeps the host work where it was: the
+// counts when the order is asked for, then, in the loop that fills the caller's own device
+// entries, place() for the batch indices taken in order.
+struct SeriesOrder {
+  int64_t G = 0, n_vis = 0;      // groups; the visible series (keys 0 .. G) come first
+  std::vector<int64_t> cur;      // [key] the next position of that key
+  std::vector<int64_t> orig;     // [position] batch index (the new h_orig)
+  std::vector<int32_t> group;    // [position] key (the new h_group)
+  void begin_fill(int64_t N) {
+    orig.resize(N);
+    group.resize(N);
+  }
+  int64_t place(int64_t b, int64_t k) {
+    const int64_t i = cur[k]++;
+    orig[i] = b;
+    group[i] = (int32_t)k;
+    return i;
+  }
+};
+template <class Key> static SeriesOrder order_by_key(int64_t N, int64_t G, Key key) {
+  SeriesOrder o;
+  o.G = G;
+  std::vector<int64_t> start(G + 3, 0);
+  for (int64_t b = 0; b < N; b++) start[key(b) + 1]++;
+  for (int64_t k = 0; k < G + 2; k++) start[k + 1] += start[k];
+  o.n_vis = start[G + 1];
+  o.cur.assign(start.begin(), start.end() - 1);
+  return o;
+}
+
+// The host mirrors of the edited batch: filled beside the resident ones from a download of the
+// gathered descriptors -- a sequential pass over 48 B a row, where permuting the five old mirrors
+// is five cache misses a row (17 ms against 34 ms for a million scattered one-row series,
+// profiles/regroup/regroup_dl_*.log) -- and swapped in at the commit.  The caller fills srp, and
+// keeps its own synchronize (and trace marks) between download and split.
+struct Mirrors {
+  std::vector<int64_t> srp;   // [series + 1]
+  std::vector<uint32_t> base, ndp, qlen, vlen, flags;
+  std::vector<RegRow> reg;
+  // queues the copies of rows2 (into rg_rows, which the caller has sized) and reg2, nr rows each
+  hipError_t download(tsdbhip_ctx* c, int64_t nr) {
+    hipError_t e = hipSuccess;
+    if (nr) e = hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)nr * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream);
+    reg.resize(nr);
+    if (nr && e == hipSuccess)
+      e = hipMemcpyAsync(reg.data(), c->reg2.p, (size_t)nr * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream);
+    return e;
+  }
+  // the per-row mirrors, sized while the device works ...
+  void size_rows() {
+    for (auto* v : {&base, &ndp, &qlen, &vlen, &flags}) v->resize(reg.size());
+  }
+  // ... and filled after the caller's hipStreamSynchronize
+  void split(const tsdbhip_ctx* c) {
+    split_rows(reinterpret_cast<const RowDesc*>(c->rg_rows.p), (int64_t)reg.size(), base, ndp, qlen, vlen, flags);
+  }
+  // From here on the context holds the edited batch.  order: the series' new order and groups; null
+  // when the edit leaves the order, the groups and the exclusions as they are (tsdbhip_trim).
+  void commit(tsdbhip_ctx* c, SeriesOrder* order) {
+    std::swap(c->rows, c->rows2);
+    std::swap(c->reg, c->reg2);
+    std::swap(c->srp, c->srp2);
+    c->h_reg.swap(reg);
+    c->h_srp.swap(srp);
+    c->h_base.swap(base);
+    c->h_ndp.swap(ndp);
+    c->h_qlen.swap(qlen);
+    c->h_vlen.swap(vlen);
+    c->h_flags.swap(flags);
+    const int64_t N = (int64_t)c->h_srp.size() - 1;
+    if (order) {
+      std::swap(c->gid, c->gid2);
+      c->h_orig.swap(order->orig);
+      c->h_group.swap(order->group);
+      c->n_series = order->n_vis;
+      c->n_groups = order->G;
+    }
+    c->n_series_loaded = N;
+    c->n_rows_loaded = c->h_srp[N];
+    c->n_rows = c->h_srp[c->n_series];
+    c->max_series_rows = 0;
+    for (int64_t i = 0; i < c->n_series; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
+    if (!order) return;
+    if (c->n_series == N) {
+      c->h_excl.clear();
+    } else {
+      c->h_excl.assign(N, 0);
+      for (int64_t i = c->n_series; i < N; i++) c->h_excl[c->h_orig[i]] = 1;
+    }
+  }
+};
+
+// What the index passes of one edit share -- the delta's and the suspects' in tsdbhip_upsert: the
+// blobs as a pass reads them, the route (finish_load's rules), the int16 value copy (null while
+// there is none) and the DevBuf that one allocated on demand goes into.  Whose that DevBuf is
+// decides whether such a copy can outlive the call.
+struct IndexPlan {
+  const std::string* fn = nullptr;   // for edit_nomem
+  const char* nomem_hint = "";
+  const uint8_t* qp = nullptr;       // the qualifier and value blobs
+  const uint8_t* vp = nullptr;
+  uint8_t* v2p = nullptr;
+  DevBuf* v2_buf = nullptr;
+  size_t qcap = 0;                   // the qualifier blob's capacity (val2 lives at qualifier offsets)
+  bool generic = false, fused = false;
+  int need_v2() {
+    if (v2p) return 0;
+    const hipError_t e = v2_buf->ensure(qcap);
+    if (e != hipSuccess) return edit_nomem(*fn, e, nomem_hint);
+    v2p = v2_buf->as<uint8_t>();
+    return 0;
+  }
+  // the short rows are indexed by the classifying pass when a val2 fits beside the batch with room to spare
+  int choose_route() {
+    if (generic || opt_off(OPT_INDEX_FUSED) || !fused_index_fits(qcap)) return 0;
+    if (const int rc = need_v2()) return rc;
+    fused = true;
+    return 0;
+  }
+};
+
+// One index pass over n descriptors in an array of their own; cnt: the pass's class counts
+// (tsdbhip_debug_index), k_index_short's hand-backs riding along on the stream as in finish_load.
+static int index_pass(tsdbhip_ctx* c, IndexPlan& ip, RowDesc* rows, RegRow* reg, int64_t n, IndexClasses& ik, uint32_t* cnt) {
+  const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
+  int32_t* const err = c->err.as<int32_t>();
+  if (ip.fused)
+    HIP_OK(index_fused(ip.qp, ip.vp, ip.v2p, rows, reg, ib, n, err, &ik, c->stream));
+  else
+    HIP_OK(index_classes(ip.qp, rows, ib, n, &ik, c->stream));
+  if (!ip.fused && ik.vle_capable && !ip.generic)
+    if (const int rc = ip.need_v2()) return rc;
+  HIP_OK(index_rows(ip.qp, ip.vp, ip.generic ? nullptr : ip.v2p, rows, reg, ib, ik, n, err, ip.generic, c->stream));
+  if (!ip.generic) {
+    std::memcpy(cnt, ik.cnt, 16 * sizeof(uint32_t));
+    if (!ip.fused) cnt[IDX_C_FAIL] = 0;
+    if (!ip.fused && ik.short_rows)
+      HIP_OK(hipMemcpyAsync(&cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  return 0;
+}
+
+// The suspects of tsdbhip_trim and tsdbhip_upsert: kept rows that carry ROW_UNSORTED and follow a
+// row that went, which may have been the flag's cause.  They are staged into an array of their
+// own, indexed again as a delta is -- between ev[2] and ev[3] -- and written back; the caller then
+// runs k_recede's walk over its own list of their series.  sus: their positions in rows2.
+// reindex_ensure allocates and queues nothing.
+static int reindex_ensure(tsdbhip_ctx* c, int64_t n_sus) {
+  HIP_OK(c->tr_list.ensure((size_t)n_sus * 8));
+  HIP_OK(c->tr_rows.ensure((size_t)n_sus * sizeof(RowDesc)));
+  HIP_OK(c->tr_reg.ensure((size_t)n_sus * sizeof(RegRow)));
+  HIP_OK(c->hint.ensure(n_sus));
+  HIP_OK(c->ilist.ensure(n_sus * 4));
+  HIP_OK(c->icnt.ensure(32 * 4));
+  return 0;
+}
+static int reindex_suspects(tsdbhip_ctx* c, IndexPlan& ip, const int64_t* sus, int64_t n_sus, uint32_t* cnt) {
+  HIP_OK(hipMemcpyAsync(c->tr_list.p, sus, (size_t)n_sus * 8, hipMemcpyHostToDevice, c->stream));
+  const int64_t* const list = c->tr_list.as<int64_t>();
+  RowDesc* const srows = c->tr_rows.as<RowDesc>();
+  RegRow* const sreg = c->tr_reg.as<RegRow>();
+  HIP_OK(launch_trim_stage(c->rows2.as<RowDesc>(), list, n_sus, srows, c->stream));
+  IndexClasses ik{};
+  HIP_OK(hipEventRecord(c->ev[2], c->stream));
+  if (const int rc = index_pass(c, ip, srows, sreg, n_sus, ik, cnt)) return rc;
+  HIP_OK(hipEventRecord(c->ev[3], c->stream));
+  HIP_OK(launch_trim_unstage(srows, sreg, list, n_sus, c->rows2.as<RowDesc>(), c->reg2.as<RegRow>(), c->stream));
+  return 0;
 }
 
 // New group ids and tag-filter verdicts for the resident series: the series'
@@ -2591,32 +2856,21 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   if (N == 0) return 0;
   HIP_OK(hipSetDevice(c->device));
   const int64_t G = (int64_t)maxg + 1;
-  // the new order: current resident positions, stably sorted by (key, batch index).  Keys are
-  // the group, G for an ungrouped series, G + 1 for an excluded one; the sort is a counting sort
-  // over the positions taken in batch order (pos: batch index -> current position).
+  // the new order of the current resident positions (pos: batch index -> current position)
   std::vector<int32_t> pos(N);
   for (int64_t i = 0; i < N; i++) pos[c->h_orig[i]] = (int32_t)i;
   auto key = [&](int64_t b) -> int64_t {
     const int32_t g = group_id[b];
     return g == TSDB_GROUP_EXCLUDED ? G + 1 : g < 0 ? G : g;
   };
-  std::vector<int64_t> start(G + 3, 0);
-  for (int64_t b = 0; b < N; b++) start[key(b) + 1]++;
-  for (int64_t k = 0; k < G + 2; k++) start[k + 1] += start[k];
-  const int64_t n_vis = start[G + 1];
+  SeriesOrder order = order_by_key(N, G, key);
   HIP_OK(c->rg_stage.ensure((size_t)N * sizeof(int2)));
   int2* ent = reinterpret_cast<int2*>(c->rg_stage.p);
-  std::vector<int64_t> n_orig(N);
-  std::vector<int32_t> n_group(N);
-  {
-    std::vector<int64_t> cur(start.begin(), start.end() - 1);
-    for (int64_t b = 0; b < N; b++) {
-      const int64_t k = key(b), i = cur[k]++;
-      ent[i].x = pos[b];
-      ent[i].y = (int32_t)k;
-      n_orig[i] = b;
-      n_group[i] = (int32_t)k;
-    }
+  order.begin_fill(N);
+  for (int64_t b = 0; b < N; b++) {
+    const int64_t k = key(b), i = order.place(b, k);
+    ent[i].x = pos[b];
+    ent[i].y = (int32_t)k;
   }
   // device: the new series_row_ptr, descriptors and gid into the second buffers
   HIP_OK(c->rg_ent.ensure((size_t)N * sizeof(int2)));
@@ -2638,67 +2892,17 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   rp.reg_new = c->reg2.as<RegRow>();
   HIP_OK(regroup_scan(rp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
   HIP_OK(launch_regroup(rp, c->stream));
-  // host mirrors in the new order: series_row_ptr from the old one while the device works, the
-  // per-row mirrors from a download of the gathered descriptors -- a sequential pass over 48 B a
-  // row, where permuting the five old mirrors is five cache misses a row (17 ms against 34 ms
-  // for a million scattered one-row series, profiles/regroup/regroup_dl_*.log)
+  // host mirrors in the new order: series_row_ptr from the old one while the device works
+  Mirrors m;
   HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RowDesc)));
-  if (NR)
-    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
-  std::vector<RegRow> n_reg(NR);
-  if (NR) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
-  std::vector<int64_t> n_srp(N + 1, 0);
-  for (int64_t i = 0; i < N; i++) n_srp[i + 1] = n_srp[i] + (c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x]);
-  std::vector<uint32_t> n_base(NR), n_ndp(NR), n_qlen(NR), n_vlen(NR), n_flags(NR);
+  HIP_OK(m.download(c, NR));
+  m.srp.assign(N + 1, 0);
+  for (int64_t i = 0; i < N; i++) m.srp[i + 1] = m.srp[i] + (c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x]);
+  m.size_rows();
   HIP_OK(hipStreamSynchronize(c->stream));
-  {
-    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
-    for (int64_t r = 0; r < NR; r++) {
-      n_base[r] = back[r].base;
-      n_ndp[r] = back[r].ndp;
-      n_qlen[r] = back[r].qlen;
-      n_vlen[r] = back[r].vlen;
-      n_flags[r] = back[r].flags;
-    }
-  }
-  // commit: from here on the context holds the new grouping
-  std::swap(c->rows, c->rows2);
-  std::swap(c->reg, c->reg2);
-  c->h_reg.swap(n_reg);
-  std::swap(c->srp, c->srp2);
-  std::swap(c->gid, c->gid2);
-  c->h_srp.swap(n_srp);
-  c->h_base.swap(n_base);
-  c->h_ndp.swap(n_ndp);
-  c->h_qlen.swap(n_qlen);
-  c->h_vlen.swap(n_vlen);
-  c->h_flags.swap(n_flags);
-  c->h_orig.swap(n_orig);
-  c->h_group.swap(n_group);
-  c->n_series = n_vis;
-  c->n_rows = c->h_srp[n_vis];
-  c->n_groups = G;
-  c->max_series_rows = 0;
-  for (int64_t i = 0; i < n_vis; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
-  if (n_vis == N) {
-    c->h_excl.clear();
-  } else {
-    c->h_excl.assign(N, 0);
-    for (int64_t i = n_vis; i < N; i++) c->h_excl[c->h_orig[i]] = 1;
-  }
-  // what a load invalidates of the state that depends on the series' order or groups
-  c->none_tiles_ready = false;
-  c->acct_valid = false;
-  c->seqd_valid = false;
-  c->row_ser_valid = false;
-  c->n_grouped = -1;
-  c->mdp_valid = false;
-  c->ro_meta_valid = false;
-  c->lc_valid = false;
-  c->calc_valid = false;
-  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the grouping they came from)
-  c->pg.cells = 0;
-  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  m.split(c);
+  m.commit(c, &order);
+  invalidate_derived(c);
   return finish_classes(c);
 }
 
@@ -2706,13 +2910,13 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
 // the blobs' tail and are indexed in a descriptor array of their own; k_append then gathers the
 // kept resident descriptors and the delta's into the series order a fresh load of the merged
 // batch, regrouped to the present ids, would have.  Everything is validated and allocated before
-// the resident batch changes; the commit is the swap at the end, as in tsdbhip_regroup.
+// the resident batch changes; the commit is the swap at the end.
 //
 // tsdbhip_upsert is the same call without the restriction to a tail scan: a delta
 // row goes wherever base order puts it in its series and replaces the resident row of its base.
 // Which rows replace one is found on the device (k_upsert_rank), the gather is k_upsert's merge of
 // two sorted lists, kept rows whose ROW_UNSORTED a replaced row may have caused are indexed again
-// as tsdbhip_trim indexes its suspects, and k_recede's walk may flag any row of a touched series.
+// (reindex_suspects), and k_recede's walk may flag any row of a touched series.
 struct MergeInfo {
   int64_t series_added = 0, rows_added = 0, rows_replaced = 0, rows_reindexed = 0;
   bool grew = false;
@@ -2726,23 +2930,9 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   if (!c->regroup_ok)
     return fail(TSDB_E_NOT_IMPLEMENTED, fn + " needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
                                              "tsdbhip_synth (a shard's groups are numbered globally)");
-  // the delta's own batch invariants (load_body's checks)
+  // the delta's own batch invariants, every series and row of it
   const tsdbhip_batch* b = delta;
-  if (b->n_series < 0 || b->n_rows < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "negative sizes");
-  if (b->n_series > 0 && (!b->series_row_ptr || !b->group_id || !series_index || !series_new))
-    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
-  if (b->n_rows > 0 && (!b->row_base_time || !b->row_qual_off || !b->row_val_off || !b->qual || !b->val))
-    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null batch arrays");
-  if (b->n_series > 0 && (b->series_row_ptr[0] != 0 || b->series_row_ptr[b->n_series] != b->n_rows))
-    return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr does not cover the rows");
-  for (int64_t s = 0; s < b->n_series; s++)
-    if (b->series_row_ptr[s + 1] < b->series_row_ptr[s]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "series_row_ptr not monotonic");
-  for (int64_t r = 0; r < b->n_rows; r++) {
-    if (b->row_qual_off[r + 1] < b->row_qual_off[r] || b->row_val_off[r + 1] < b->row_val_off[r])
-      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row offsets not monotonic");
-    if (b->row_qual_off[r + 1] - b->row_qual_off[r] > 0xFFFFFFFFull || b->row_val_off[r + 1] - b->row_val_off[r] > 0xFFFFFFFFull)
-      return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
-  }
+  if (const int rc = check_batch(b, !series_index || !series_new, true)) return rc;
   const int64_t D = b->n_series;
   if (D == 0) return 0;
   // rows of the delta that share (series, base) merge first, as at load
@@ -2834,10 +3024,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     const int32_t g = c->h_group[pos[old_of[x]]];
     return g < G_old ? g : g == G_old ? G : G + 1;
   };
-  std::vector<int64_t> start(G + 3, 0);
-  for (int64_t x = 0; x < N2; x++) start[key(x) + 1]++;
-  for (int64_t k = 0; k < G + 2; k++) start[k + 1] += start[k];
-  const int64_t n_vis = start[G + 1];
+  SeriesOrder order = order_by_key(N2, G, key);
   // staging of the delta's cells at the blobs' tail, 16-byte aligned
   std::vector<RowDesc> rd(DR);
   const uint64_t q0 = align16(c->qual_bytes), v0 = align16(c->val_bytes);   // the tail: where the delta's cells go
@@ -2861,19 +3048,11 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   pack_cells(hq.get(), hv.get(), b, drow.data(), rd.data(), DR, q0, v0);
   HIP_OK(hipSetDevice(c->device));
   // ---- allocations: nothing of the resident batch is released before the commit ----
-  struct Hold {   // what the call allocated and has not handed to the context
-    DevBuf q, v, v2;
-    ~Hold() { q.release(); v.release(); v2.release(); }
-  } hold;
+  BlobHold hold;
   const bool had_val2 = c->val2.p != nullptr;
-  const int64_t reserve = opt(OPT_APPEND_RESERVE) < 0 ? 50 : opt(OPT_APPEND_RESERVE);
-  auto grown = [&](uint64_t need) { return (size_t)(need + need / 100 * reserve + need % 100 * reserve / 100); };
   const bool grow_q = !c->qual.p || qtot + BLOB_SLACK > c->qual.n, grow_v = !c->val.p || vtot + BLOB_SLACK > c->val.n;
-  auto nomem = [&](hipError_t e) {
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, fn + ": the grown blobs do not fit beside the resident ones")
-                                    : fail(TSDB_E_HIP, fn + ": " + hipGetErrorString(e));
-  };
+  const char* const nomem_hint = "the grown blobs do not fit beside the resident ones";
+  auto nomem = [&](hipError_t e) { return edit_nomem(fn, e, nomem_hint); };
   hipError_t he;
   if (grow_q && (he = hold.q.ensure(grown(qtot + BLOB_SLACK))) != hipSuccess) return nomem(he);
   if (grow_v && (he = hold.v.ensure(grown(vtot + BLOB_SLACK))) != hipSuccess) return nomem(he);
@@ -2904,33 +3083,21 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   // val2 for the delta's index pass, by finish_load's rule; a copy the resident rows lacked is
   // allocated at the qualifier blob's capacity (resident rows never read it)
   const bool generic = opt_is(OPT_INDEX_GENERIC, 1);
-  bool fused = false;
-  uint8_t* v2p = grow_v2 ? hold.v2.as<uint8_t>() : c->val2.as<uint8_t>();   // (null when there was none)
-  if (!generic) {
-    size_t fr = 0, tot = 0;
-    if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > qcap + ((size_t)8 << 30)) {
-      if (!v2p) {
-        if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
-        v2p = hold.v2.as<uint8_t>();
-      }
-      fused = true;
-    }
-  }
+  IndexPlan ip;
+  ip.fn = &fn;
+  ip.nomem_hint = nomem_hint;
+  ip.qp = qp;
+  ip.vp = vp;
+  ip.v2p = grow_v2 ? hold.v2.as<uint8_t>() : c->val2.as<uint8_t>();   // (null when there was none)
+  ip.v2_buf = &hold.v2;
+  ip.qcap = qcap;
+  ip.generic = generic;
+  if (const int rc = ip.choose_route()) return rc;
   // ---- queued work: the cells, the delta's index, the merge-gather ----
   hipEvent_t* ev = c->ev;
-  // option TRACE: the stages by hipEvents of the call's own (stream time between stage ends, the
-  // host work in between included), on stderr
-  struct Trace {
-    hipEvent_t e[11] = {};   // (6 .. 10: tsdbhip_upsert's stages)
-    bool on = false;
-    ~Trace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-  } tr;
-  if (opt_is(OPT_TRACE, 1)) {
-    tr.on = true;
-    for (auto& x : tr.e) HIP_OK(hipEventCreate(&x));
-  }
-  auto mark = [&](int i) { return tr.on ? hipEventRecord(tr.e[i], c->stream) : hipSuccess; };
-  HIP_OK(mark(0));
+  StageTrace<11> tr;   // (6 .. 10: tsdbhip_upsert's stages)
+  HIP_OK(tr.begin(c->stream));
+  HIP_OK(tr.mark(0));
   if (grow_q) {
     if (c->qual_bytes) HIP_OK(hipMemcpyAsync(qp, c->qual.p, c->qual_bytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_OK(hipMemsetAsync(qp + c->qual_bytes, 0, qcap - c->qual_bytes, c->stream));
@@ -2941,35 +3108,32 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     if (c->val_bytes) HIP_OK(hipMemcpyAsync(vp, c->val.p, c->val_bytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_OK(hipMemsetAsync(vp + c->val_bytes, 0, hold.v.n - c->val_bytes, c->stream));
   }
-  HIP_OK(mark(1));
+  HIP_OK(tr.mark(1));
   if (hq_n) HIP_OK(h2d(c, qp + q0, hq.get(), hq_n, c->stream));
   if (hv_n) HIP_OK(h2d(c, vp + v0, hv.get(), hv_n, c->stream));
   if (!grow_q) HIP_OK(hipMemsetAsync(qp + qtot, 0, BLOB_SLACK, c->stream));   // (the slack past the new end reads as zeros)
   if (!grow_v) HIP_OK(hipMemsetAsync(vp + vtot, 0, BLOB_SLACK, c->stream));
   if (DR) HIP_OK(hipMemcpyAsync(c->ap_rows.p, rd.data(), (size_t)DR * sizeof(RowDesc), hipMemcpyHostToDevice, c->stream));
-  // the entries of the new order: a counting sort by (key, new batch index)
+  // the entries of the new order
   int4* ent = reinterpret_cast<int4*>(c->ap_stage.p);
   int32_t* touched = reinterpret_cast<int32_t*>(ent + N2);
   int64_t n_touched = 0;
-  std::vector<int64_t> n_orig(N2), n_srp(N2 + 1, 0);
-  std::vector<int32_t> n_group(N2);
-  {
-    std::vector<int64_t> cur(start.begin(), start.end() - 1);
-    for (int64_t x = 0; x < N2; x++) {
-      const int64_t k = key(x), i = cur[k]++;
-      const int32_t di = delta_of[x];
-      ent[i].x = is_new[x] ? -1 : pos[old_of[x]];
-      ent[i].y = (int32_t)k;
-      ent[i].z = di >= 0 ? d0[di] : 0;
-      ent[i].w = di >= 0 ? (dn[di] | (repl[di] ? APPEND_REPLACE : 0)) : 0;
-      n_orig[i] = x;
-      n_group[i] = (int32_t)k;
-      if (di >= 0 && dn[di] > 0) touched[n_touched++] = (int32_t)i;
-    }
-    for (int64_t i = 0; i < N2 && !upsert; i++) {   // (upsert: once the replaced rows are known)
-      const int64_t res = ent[i].x >= 0 ? c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x] : 0;
-      n_srp[i + 1] = n_srp[i] + res - ((ent[i].w & APPEND_REPLACE) ? 1 : 0) + (ent[i].w & ~APPEND_REPLACE);
-    }
+  Mirrors m;
+  std::vector<int64_t>& n_srp = m.srp;
+  order.begin_fill(N2);
+  n_srp.assign(N2 + 1, 0);
+  for (int64_t x = 0; x < N2; x++) {
+    const int64_t k = key(x), i = order.place(x, k);
+    const int32_t di = delta_of[x];
+    ent[i].x = is_new[x] ? -1 : pos[old_of[x]];
+    ent[i].y = (int32_t)k;
+    ent[i].z = di >= 0 ? d0[di] : 0;
+    ent[i].w = di >= 0 ? (dn[di] | (repl[di] ? APPEND_REPLACE : 0)) : 0;
+    if (di >= 0 && dn[di] > 0) touched[n_touched++] = (int32_t)i;
+  }
+  for (int64_t i = 0; i < N2 && !upsert; i++) {   // (upsert: once the replaced rows are known)
+    const int64_t res = ent[i].x >= 0 ? c->h_srp[ent[i].x + 1] - c->h_srp[ent[i].x] : 0;
+    n_srp[i + 1] = n_srp[i] + res - ((ent[i].w & APPEND_REPLACE) ? 1 : 0) + (ent[i].w & ~APPEND_REPLACE);
   }
   if (!upsert && n_srp[N2] != NR2) return fail(TSDB_E_HIP, "tsdbhip_append: row count mismatch (internal)");
   HIP_OK(hipMemcpyAsync(c->ap_ent.p, ent, (size_t)N2 * sizeof(int4), hipMemcpyHostToDevice, c->stream));
@@ -2982,32 +3146,12 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
   RowDesc* drows = c->ap_rows.as<RowDesc>();
   RegRow* dreg = c->ap_reg.as<RegRow>();
-  HIP_OK(mark(2));
+  HIP_OK(tr.mark(2));
   HIP_OK(hipEventRecord(ev[2], c->stream));
-  // one index pass over descriptors in an array of their own, under finish_load's rules: the
-  // delta's rows and, in tsdbhip_upsert, the suspect rows
-  auto index_pass = [&](RowDesc* rows_, RegRow* reg_, int64_t n, const IndexBufs& ib_, IndexClasses& ik_, uint32_t* cnt) -> int {
-    if (fused)
-      HIP_OK(index_fused(qp, vp, v2p, rows_, reg_, ib_, n, c->err.as<int32_t>(), &ik_, c->stream));
-    else
-      HIP_OK(index_classes(qp, rows_, ib_, n, &ik_, c->stream));
-    if (!fused && ik_.vle_capable && !generic && !v2p) {
-      if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
-      v2p = hold.v2.as<uint8_t>();
-    }
-    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, rows_, reg_, ib_, ik_, n, c->err.as<int32_t>(), generic, c->stream));
-    if (!generic) {
-      std::memcpy(cnt, ik_.cnt, 16 * sizeof(uint32_t));
-      if (!fused) cnt[IDX_C_FAIL] = 0;
-      if (!fused && ik_.short_rows)
-        HIP_OK(hipMemcpyAsync(&cnt[IDX_C_FAIL], ib_.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    return 0;
-  };
   IndexClasses ik{};
   uint32_t idx_cnt[16] = {};
   if (DR) {
-    const int rc = index_pass(drows, dreg, DR, ib, ik, idx_cnt);
+    const int rc = index_pass(c, ip, drows, dreg, DR, ik, idx_cnt);
     if (rc) return rc;
   }
   HIP_OK(hipEventRecord(ev[3], c->stream));
@@ -3023,9 +3167,9 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     rp.lb = c->up_lb.as<int32_t>();
     rp.hit = c->up_hit.as<int32_t>();
     HIP_OK(launch_upsert_rank(rp, c->stream));
-    HIP_OK(mark(6));
+    HIP_OK(tr.mark(6));
     HIP_OK(upsert_scan_hits(rp.hit, c->up_S.as<int32_t>(), DR, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
-    HIP_OK(mark(7));
+    HIP_OK(tr.mark(7));
     h_lb.resize(DR);
     h_hit.resize(DR);
     if (DR) {
@@ -3041,14 +3185,11 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     HIP_OK(hipStreamSynchronize(c->stream));
     (void)hipEventElapsedTime(&t_index, ev[2], ev[3]);
     for (const RowDesc& d : rd)
-      if ((d.flags & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2)) { need_val2 = true; break; }
+      if (row_wants_val2(d.flags)) { need_val2 = true; break; }
     if (need_val2 && generic) {   // test hook: the sequential path writes the copy in a second pass
-      if (!v2p) {
-        if ((he = hold.v2.ensure(qcap)) != hipSuccess) return nomem(he);
-        v2p = hold.v2.as<uint8_t>();
-      }
+      if (const int rc = ip.need_v2()) return rc;
       HIP_OK(hipEventRecord(ev[2], c->stream));
-      HIP_OK(index_rows(qp, vp, v2p, drows, dreg, ib, ik, DR, c->err.as<int32_t>(), true, c->stream));
+      HIP_OK(index_rows(qp, vp, ip.v2p, drows, dreg, ib, ik, DR, c->err.as<int32_t>(), true, c->stream));
       HIP_OK(hipEventRecord(ev[3], c->stream));
       HIP_OK(hipStreamSynchronize(c->stream));
       float t2 = 0;
@@ -3056,7 +3197,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
       t_index += t2;
     }
   }
-  HIP_OK(mark(3));
+  HIP_OK(tr.mark(3));
   AppendParams ap{};
   ap.ent = c->ap_ent.as<int4>();
   ap.srp_old = c->srp.as<int64_t>();
@@ -3123,76 +3264,39 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     up.reg_old = ap.reg_old;
     up.reg_delta = dreg;
     up.reg_new = ap.reg_new;
-    HIP_OK(mark(8));
+    HIP_OK(tr.mark(8));
     HIP_OK(upsert_scan(up, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
     HIP_OK(launch_upsert(up, c->stream));
-    HIP_OK(mark(9));
-    if (n_sus) {   // indexed again exactly as tsdbhip_trim indexes its suspects, before the walk
-      HIP_OK(c->tr_list.ensure((size_t)n_sus * 8));
-      HIP_OK(c->tr_rows.ensure((size_t)n_sus * sizeof(RowDesc)));
-      HIP_OK(c->tr_reg.ensure((size_t)n_sus * sizeof(RegRow)));
-      HIP_OK(c->hint.ensure(std::max<int64_t>(DR, n_sus)));
-      HIP_OK(c->ilist.ensure(std::max<int64_t>(DR, n_sus) * 4));
-      HIP_OK(hipMemcpyAsync(c->tr_list.p, sus.data(), (size_t)n_sus * 8, hipMemcpyHostToDevice, c->stream));
-      RowDesc* const srows = c->tr_rows.as<RowDesc>();
-      RegRow* const sreg = c->tr_reg.as<RegRow>();
-      HIP_OK(launch_trim_stage(up.rows_new, c->tr_list.as<int64_t>(), n_sus, srows, c->stream));
-      const IndexBufs sib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
-      IndexClasses sik{};
-      HIP_OK(hipEventRecord(ev[2], c->stream));
-      const int rc = index_pass(srows, sreg, n_sus, sib, sik, sus_cnt);
-      if (rc) return rc;
-      HIP_OK(hipEventRecord(ev[3], c->stream));
-      HIP_OK(launch_trim_unstage(srows, sreg, c->tr_list.as<int64_t>(), n_sus, up.rows_new, up.reg_new, c->stream));
+    HIP_OK(tr.mark(9));
+    if (n_sus) {   // indexed again before the walk (the delta's pass is through with hint / ilist)
+      if (const int rc = reindex_ensure(c, n_sus)) return rc;
+      if (const int rc = reindex_suspects(c, ip, sus.data(), n_sus, sus_cnt)) return rc;
       HIP_OK(hipStreamSynchronize(c->stream));   // (sus is pageable; the pass's time)
       (void)hipEventElapsedTime(&t_sus, ev[2], ev[3]);
     }
-    HIP_OK(mark(10));
+    HIP_OK(tr.mark(10));
     HIP_OK(launch_trim_recede(up.rows_new, up.reg_new, up.srp_new, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
   }
-  HIP_OK(mark(4));
-  if (NR2)
-    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
-  std::vector<RegRow> n_reg(NR2);
-  if (NR2) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR2 * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(mark(5));
-  std::vector<uint32_t> n_base(NR2), n_ndp(NR2), n_qlen(NR2), n_vlen(NR2), n_flags(NR2);
+  HIP_OK(tr.mark(4));
+  HIP_OK(m.download(c, NR2));
+  HIP_OK(tr.mark(5));
+  m.size_rows();
   HIP_OK(hipStreamSynchronize(c->stream));
   if (tr.on) {
     float t[5] = {};
-    for (int i = 0; i < 5; i++) (void)hipEventElapsedTime(&t[i], tr.e[i], tr.e[i + 1]);
+    for (int i = 0; i < 5; i++) t[i] = tr.ms(i, i + 1);
     if (!upsert) {
       std::fprintf(stderr, "[trace append] grow_copy %.3f upload %.3f index %.3f scan_gather %.3f desc_download %.3f ms\n",
                    t[0], t[1], t[2], t[3], t[4]);
     } else {   // (rank_download: the ranks' way to the host and the host's pass over them)
-      float rank = 0, scan = 0, dl = 0, gather = 0, sus = 0, recede = 0;
-      (void)hipEventElapsedTime(&rank, tr.e[2], tr.e[6]);
-      (void)hipEventElapsedTime(&scan, tr.e[6], tr.e[7]);
-      (void)hipEventElapsedTime(&dl, tr.e[7], tr.e[8]);
-      (void)hipEventElapsedTime(&gather, tr.e[8], tr.e[9]);
-      (void)hipEventElapsedTime(&sus, tr.e[9], tr.e[10]);
-      (void)hipEventElapsedTime(&recede, tr.e[10], tr.e[4]);
       std::fprintf(stderr, "[trace upsert] grow_copy %.3f upload %.3f index_rank %.3f (delta_index %.3f) hit_scan %.3f rank_download %.3f "
                            "scan_gather %.3f suspects %.3f (suspect_index %.3f) recede %.3f desc_download %.3f ms\n",
-                   t[0], t[1], rank, t_index, scan, dl, gather, sus, t_sus, recede, t[4]);
+                   t[0], t[1], tr.ms(2, 6), t_index, tr.ms(6, 7), tr.ms(7, 8), tr.ms(8, 9), tr.ms(9, 10), t_sus, tr.ms(10, 4), t[4]);
     }
   }
-  {
-    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
-    for (int64_t r = 0; r < NR2; r++) {
-      n_base[r] = back[r].base;
-      n_ndp[r] = back[r].ndp;
-      n_qlen[r] = back[r].qlen;
-      n_vlen[r] = back[r].vlen;
-      n_flags[r] = back[r].flags;
-    }
-  }
+  m.split(c);
   // ---- commit: from here on the context holds the merged batch ----
-  std::swap(c->rows, c->rows2);
-  std::swap(c->reg, c->reg2);
-  c->h_reg.swap(n_reg);
-  std::swap(c->srp, c->srp2);
-  std::swap(c->gid, c->gid2);
+  m.commit(c, &order);
   if (grow_q) std::swap(c->qual, hold.q);
   if (grow_v) std::swap(c->val, hold.v);
   if (had_val2 ? grow_v2 : (hold.v2.p && need_val2)) std::swap(c->val2, hold.v2);
@@ -3201,27 +3305,6 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   c->val_bytes = vtot;
   c->qual_dead += dead_q;
   c->val_dead += dead_v;
-  c->h_srp.swap(n_srp);
-  c->h_base.swap(n_base);
-  c->h_ndp.swap(n_ndp);
-  c->h_qlen.swap(n_qlen);
-  c->h_vlen.swap(n_vlen);
-  c->h_flags.swap(n_flags);
-  c->h_orig.swap(n_orig);
-  c->h_group.swap(n_group);
-  c->n_series_loaded = N2;
-  c->n_rows_loaded = NR2;
-  c->n_series = n_vis;
-  c->n_rows = c->h_srp[n_vis];
-  c->n_groups = G;
-  c->max_series_rows = 0;
-  for (int64_t i = 0; i < n_vis; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
-  if (n_vis == N2) {
-    c->h_excl.clear();
-  } else {
-    c->h_excl.assign(N2, 0);
-    for (int64_t i = n_vis; i < N2; i++) c->h_excl[c->h_orig[i]] = 1;
-  }
   // tsdbhip_load_cells' compaction errors: renumbered; an entry whose row the delta brings anew
   // (the scan now returned that row) is dropped
   if (!c->cmp_errs.empty()) {
@@ -3244,27 +3327,30 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   }
   for (int k = 0; k < 16; k++) idx_cnt[k] += sus_cnt[k];   // (this call's index passes: the delta's plus the suspects')
   std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
-  c->idx_fused = fused;
+  c->idx_fused = ip.fused;
   c->index_ms = t_index + t_sus;
-  // what a load invalidates of the state that depends on the rows, the series' order or groups
-  c->none_tiles_ready = false;
-  c->acct_valid = false;
-  c->seqd_valid = false;
-  c->row_ser_valid = false;
-  c->n_grouped = -1;
-  c->mdp_valid = false;
-  c->ro_meta_valid = false;
-  c->lc_valid = false;
-  c->calc_valid = false;
-  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the batch they came from)
-  c->pg.cells = 0;
-  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  invalidate_derived(c);
   mi->series_added = K;
   mi->rows_added = DR - n_repl;
   mi->rows_replaced = n_repl;
   mi->rows_reindexed = n_sus;
   mi->grew = grow_q || grow_v;
   return finish_classes(c);
+}
+
+// the blobs' state an edit reports, and what tsdbhip_append_info and tsdbhip_upsert_info share
+template <class Info> static void fill_blob_info(Info* info, const tsdbhip_ctx* c) {
+  info->qual_capacity = c->qual.n;
+  info->val_capacity = c->val.n;
+  info->qual_dead = c->qual_dead;
+  info->val_dead = c->val_dead;
+}
+template <class Info> static void fill_edit_info(Info* info, const MergeInfo& mi, const tsdbhip_ctx* c) {
+  info->series_added = mi.series_added;
+  info->rows_added = mi.rows_added;
+  info->rows_replaced = mi.rows_replaced;
+  fill_blob_info(info, c);
+  info->grew = mi.grew ? 1 : 0;
 }
 
 extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index,
@@ -3274,14 +3360,7 @@ extern "C" int tsdbhip_append(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   MergeInfo mi;
   const int rc = merge_delta(c, delta, series_index, series_new, false, &mi);
   if (rc || !info) return rc;
-  info->series_added = mi.series_added;
-  info->rows_added = mi.rows_added;
-  info->rows_replaced = mi.rows_replaced;
-  info->qual_capacity = c->qual.n;
-  info->val_capacity = c->val.n;
-  info->qual_dead = c->qual_dead;
-  info->val_dead = c->val_dead;
-  info->grew = mi.grew ? 1 : 0;
+  fill_edit_info(info, mi, c);
   return 0;
 }
 
@@ -3292,24 +3371,17 @@ extern "C" int tsdbhip_upsert(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   MergeInfo mi;
   const int rc = merge_delta(c, delta, series_index, series_new, true, &mi);
   if (rc || !info) return rc;
-  info->series_added = mi.series_added;
-  info->rows_added = mi.rows_added;
-  info->rows_replaced = mi.rows_replaced;
+  fill_edit_info(info, mi, c);
   info->rows_reindexed = mi.rows_reindexed;
-  info->qual_capacity = c->qual.n;
-  info->val_capacity = c->val.n;
-  info->qual_dead = c->qual_dead;
-  info->val_dead = c->val_dead;
-  info->grew = mi.grew ? 1 : 0;
   return 0;
 }
 
 // Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
-// bytes.  The descriptors are gathered as in tsdbhip_regroup, with a per-series
-// skip; kept rows whose ROW_UNSORTED an evicted row may have caused are indexed again in an array
-// of their own, as tsdbhip_append indexes a delta, and k_recede's walk runs over their series; the
-// pack copies every kept row's cells into fresh blobs in descriptor order.  Everything is
-// validated and allocated before anything is queued; the commit is the swap at the end.
+// bytes.  The descriptors are gathered with a per-series skip; kept rows whose
+// ROW_UNSORTED an evicted row may have caused are indexed again in an array of their own
+// (reindex_suspects), and k_recede's walk runs over their series; the pack copies every kept row's
+// cells into fresh blobs in descriptor order.  Everything is validated and allocated before
+// anything is queued; the commit is the swap at the end.
 extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_pct, tsdbhip_trim_info* info) {
   if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
   if (pack_dead_pct > 100) return fail(TSDB_E_ILLEGAL_ARGUMENT, "pack_dead_pct above 100");
@@ -3323,10 +3395,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   if (NR >= INT32_MAX) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_trim over 2^31 - 1 rows or more");
   tsdbhip_trim_info ti{};
   auto fill_info = [&]() {
-    ti.qual_capacity = c->qual.n;
-    ti.val_capacity = c->val.n;
-    ti.qual_dead = c->qual_dead;
-    ti.val_dead = c->val_dead;
+    fill_blob_info(&ti, c);
     if (info) *info = ti;
   };
   if (!c->regroup_ok || N == 0) { fill_info(); return 0; }
@@ -3337,8 +3406,9 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   int64_t evicted = 0, emptied = 0;
   uint64_t ev_q = 0, ev_v = 0, live_q = 0, live_v = 0;
   bool need_v2_after = false;
-  auto wants_val2 = [](uint32_t f) { return (f & (ROW_QW_MASK | ROW_ALLI | ROW_VLE2 | ROW_ERR)) == (2u | ROW_ALLI | ROW_VLE2); };
-  std::vector<int64_t> n_srp(N + 1, 0);
+  Mirrors m;
+  std::vector<int64_t>& n_srp = m.srp;
+  n_srp.assign(N + 1, 0);
   for (int64_t i = 0; i < N; i++) {
     const int64_t r0 = c->h_srp[i], r1 = c->h_srp[i + 1];
     int64_t r = r0;
@@ -3353,7 +3423,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     for (; r < r1; r++) {
       live_q += align16(c->h_qlen[r]);
       live_v += align16(c->h_vlen[r]);
-      need_v2_after |= wants_val2(c->h_flags[r]);
+      need_v2_after |= row_wants_val2(c->h_flags[r]);
     }
     n_srp[i + 1] = n_srp[i] + (r1 - r0 - skip[i]);
   }
@@ -3375,24 +3445,16 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     if (n_sus > before) sus_ser[n_ser++] = (int32_t)i;
   }
   // ---- allocations: nothing of the resident batch is released before the commit ----
-  struct Hold {   // what the call allocated and has not handed to the context
-    DevBuf q, v, v2;
-    ~Hold() { q.release(); v.release(); v2.release(); }
-  } hold;
-  auto nomem = [&](hipError_t e) {
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? fail(TSDB_E_NOMEM, "tsdbhip_trim: the packed blobs do not fit beside the resident ones "
-                                                         "(retry with TSDB_TRIM_NO_PACK)")
-                                    : fail(TSDB_E_HIP, std::string("tsdbhip_trim: ") + hipGetErrorString(e));
-  };
+  BlobHold hold;
+  const std::string fn = "tsdbhip_trim";
+  const char* const nomem_hint = "the packed blobs do not fit beside the resident ones (retry with TSDB_TRIM_NO_PACK)";
+  auto nomem = [&](hipError_t e) { return edit_nomem(fn, e, nomem_hint); };
   const bool had_val2 = c->val2.p != nullptr;
   const bool pack_v2 = do_pack && had_val2 && need_v2_after;
   if (pack_v2 && c->val2.n < c->qual_bytes)
     return fail(TSDB_E_HIP, "tsdbhip_trim: the int16 value copy is shorter than the qualifier blob (internal)");
   hipError_t he;
   if (do_pack) {
-    const int64_t reserve = opt(OPT_APPEND_RESERVE) < 0 ? 50 : opt(OPT_APPEND_RESERVE);
-    auto grown = [&](uint64_t need) { return (size_t)(need + need / 100 * reserve + need % 100 * reserve / 100); };
     if ((he = hold.q.ensure(grown(live_q + BLOB_SLACK))) != hipSuccess) return nomem(he);
     if ((he = hold.v.ensure(grown(live_v + BLOB_SLACK))) != hipSuccess) return nomem(he);
     if (pack_v2 && (he = hold.v2.ensure(hold.q.n)) != hipSuccess) return nomem(he);   // (val2 lives at qualifier offsets)
@@ -3404,46 +3466,29 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RegRow)));
   HIP_OK(c->srp2.ensure((size_t)(N + 1) * 8));
   HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
-  // the suspects' index pass: val2 by finish_load's rule, as tsdbhip_append has it for a delta.  A
-  // suspect row that needs the int16 copy had it written when it was first indexed, so the pass
-  // rewrites the same bytes; a copy allocated only because index_fused wants one goes with `idx_v2`.
+  // the suspects' index pass.  A suspect row that needs the int16 copy had it written when it was
+  // first indexed, so the pass rewrites the same bytes; a copy allocated only because the pass
+  // wants one goes with `idx_v2`.
   DevBuf idx_v2;
   struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_idx_v2{idx_v2};
-  const bool generic = opt_is(OPT_INDEX_GENERIC, 1);
-  bool fused = false;
-  uint8_t* v2p = c->val2.as<uint8_t>();   // (null when there is none)
-  const size_t qcap = c->qual.n;
+  IndexPlan ip;
+  ip.fn = &fn;
+  ip.nomem_hint = nomem_hint;
+  ip.qp = c->qual.as<uint8_t>();
+  ip.vp = c->val.as<uint8_t>();
+  ip.v2p = c->val2.as<uint8_t>();   // (null when there is none)
+  ip.v2_buf = &idx_v2;
+  ip.qcap = c->qual.n;
+  ip.generic = opt_is(OPT_INDEX_GENERIC, 1);
   if (n_sus) {
-    HIP_OK(c->tr_list.ensure((size_t)n_sus * 8));
+    if (const int rc = reindex_ensure(c, n_sus)) return rc;
     HIP_OK(c->tr_ser.ensure((size_t)n_ser * 4));
-    HIP_OK(c->tr_rows.ensure((size_t)n_sus * sizeof(RowDesc)));
-    HIP_OK(c->tr_reg.ensure((size_t)n_sus * sizeof(RegRow)));
-    HIP_OK(c->hint.ensure(n_sus));
-    HIP_OK(c->ilist.ensure(n_sus * 4));
-    HIP_OK(c->icnt.ensure(32 * 4));
-    if (!generic) {
-      size_t fr = 0, tot = 0;
-      if (!opt_off(OPT_INDEX_FUSED) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > qcap + ((size_t)8 << 30)) {
-        if (!v2p) {
-          if ((he = idx_v2.ensure(qcap)) != hipSuccess) return nomem(he);
-          v2p = idx_v2.as<uint8_t>();
-        }
-        fused = true;
-      }
-    }
+    if (const int rc = ip.choose_route()) return rc;
   }
   // ---- queued work: the gather, the suspects' index and walk, the pack ----
-  struct Trace {
-    hipEvent_t e[5] = {};
-    bool on = false;
-    ~Trace() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-  } tr;
-  if (opt_is(OPT_TRACE, 1)) {
-    tr.on = true;
-    for (auto& x : tr.e) HIP_OK(hipEventCreate(&x));
-  }
-  auto mark = [&](int i) { return tr.on ? hipEventRecord(tr.e[i], c->stream) : hipSuccess; };
-  HIP_OK(mark(0));
+  StageTrace<5> tr;
+  HIP_OK(tr.begin(c->stream));
+  HIP_OK(tr.mark(0));
   HIP_OK(hipMemcpyAsync(c->tr_skip.p, skip, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
   TrimParams tp{};
   tp.skip = c->tr_skip.as<int64_t>();
@@ -3457,44 +3502,20 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   tp.reg_new = c->reg2.as<RegRow>();
   HIP_OK(trim_scan(tp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
   HIP_OK(launch_trim_gather(tp, c->stream));
-  HIP_OK(mark(1));
+  HIP_OK(tr.mark(1));
   uint32_t idx_cnt[16] = {};
   float t_index = 0;
   if (n_sus) {
-    hipEvent_t* ev = c->ev;
-    HIP_OK(hipMemcpyAsync(c->tr_list.p, sus, (size_t)n_sus * 8, hipMemcpyHostToDevice, c->stream));
+    // (the series list and the cleared error word go ahead of the suspects' own upload and staging,
+    // which touch neither)
     HIP_OK(hipMemcpyAsync(c->tr_ser.p, sus_ser, (size_t)n_ser * 4, hipMemcpyHostToDevice, c->stream));
-    RowDesc* const drows = c->tr_rows.as<RowDesc>();
-    RegRow* const dreg = c->tr_reg.as<RegRow>();
-    HIP_OK(launch_trim_stage(tp.rows_new, c->tr_list.as<int64_t>(), n_sus, drows, c->stream));
     HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
-    const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
-    const uint8_t* const qp = c->qual.as<uint8_t>();
-    const uint8_t* const vp = c->val.as<uint8_t>();
-    HIP_OK(hipEventRecord(ev[2], c->stream));
-    IndexClasses ik{};
-    if (fused)
-      HIP_OK(index_fused(qp, vp, v2p, drows, dreg, ib, n_sus, c->err.as<int32_t>(), &ik, c->stream));
-    else
-      HIP_OK(index_classes(qp, drows, ib, n_sus, &ik, c->stream));
-    if (!fused && ik.vle_capable && !generic && !v2p) {
-      if ((he = idx_v2.ensure(qcap)) != hipSuccess) return nomem(he);
-      v2p = idx_v2.as<uint8_t>();
-    }
-    HIP_OK(index_rows(qp, vp, generic ? nullptr : v2p, drows, dreg, ib, ik, n_sus, c->err.as<int32_t>(), generic, c->stream));
-    if (!generic) {
-      std::memcpy(idx_cnt, ik.cnt, sizeof(idx_cnt));
-      if (!fused) idx_cnt[IDX_C_FAIL] = 0;
-      if (!fused && ik.short_rows)
-        HIP_OK(hipMemcpyAsync(&idx_cnt[IDX_C_FAIL], ib.cnt + IDX_C_FAIL, 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_OK(hipEventRecord(ev[3], c->stream));
-    HIP_OK(launch_trim_unstage(drows, dreg, c->tr_list.as<int64_t>(), n_sus, tp.rows_new, tp.reg_new, c->stream));
-    HIP_OK(launch_trim_recede(tp.rows_new, tp.reg_new, tp.srp_new, c->tr_ser.as<int32_t>(), n_ser, qp, c->stream));
+    if (const int rc = reindex_suspects(c, ip, sus, n_sus, idx_cnt)) return rc;
+    HIP_OK(launch_trim_recede(tp.rows_new, tp.reg_new, tp.srp_new, c->tr_ser.as<int32_t>(), n_ser, ip.qp, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    (void)hipEventElapsedTime(&t_index, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&t_index, c->ev[2], c->ev[3]);
   }
-  HIP_OK(mark(2));
+  HIP_OK(tr.mark(2));
   if (do_pack) {
     HIP_OK(trim_pack_scan(tp.rows_new, NR2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp, &c->rg_tmp_bytes,
                           c->stream));
@@ -3518,35 +3539,19 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     HIP_OK(launch_trim_pack(pp, c->stream));
     HIP_OK(launch_trim_offsets(tp.rows_new, pp.qdst, pp.vdst, NR2, c->stream));
   }
-  HIP_OK(mark(3));
-  // host mirrors from a download of the final descriptors, as tsdbhip_regroup refills them
-  if (NR2)
-    HIP_OK(hipMemcpyAsync(c->rg_rows.p, c->rows2.p, (size_t)NR2 * sizeof(RowDesc), hipMemcpyDeviceToHost, c->stream));
-  std::vector<RegRow> n_reg(NR2);
-  if (NR2) HIP_OK(hipMemcpyAsync(n_reg.data(), c->reg2.p, (size_t)NR2 * sizeof(RegRow), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(mark(4));
-  std::vector<uint32_t> n_base(NR2), n_ndp(NR2), n_qlen(NR2), n_vlen(NR2), n_flags(NR2);
+  HIP_OK(tr.mark(3));
+  // host mirrors from a download of the final descriptors
+  HIP_OK(m.download(c, NR2));
+  HIP_OK(tr.mark(4));
+  m.size_rows();
   HIP_OK(hipStreamSynchronize(c->stream));
-  if (tr.on) {
-    float t[4] = {};
-    for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&t[i], tr.e[i], tr.e[i + 1]);
-    std::fprintf(stderr, "[trace trim] scan_gather %.3f reindex %.3f pack %.3f desc_download %.3f ms\n", t[0], t[1], t[2], t[3]);
-  }
-  {
-    const RowDesc* back = reinterpret_cast<const RowDesc*>(c->rg_rows.p);
-    for (int64_t r = 0; r < NR2; r++) {
-      n_base[r] = back[r].base;
-      n_ndp[r] = back[r].ndp;
-      n_qlen[r] = back[r].qlen;
-      n_vlen[r] = back[r].vlen;
-      n_flags[r] = back[r].flags;
-    }
-  }
-  // ---- commit: from here on the context holds the trimmed batch ----
-  std::swap(c->rows, c->rows2);
-  std::swap(c->reg, c->reg2);
-  c->h_reg.swap(n_reg);
-  std::swap(c->srp, c->srp2);
+  if (tr.on)
+    std::fprintf(stderr, "[trace trim] scan_gather %.3f reindex %.3f pack %.3f desc_download %.3f ms\n", tr.ms(0, 1), tr.ms(1, 2),
+                 tr.ms(2, 3), tr.ms(3, 4));
+  m.split(c);
+  // ---- commit: from here on the context holds the trimmed batch; the series' order, groups and
+  // exclusions stay ----
+  m.commit(c, nullptr);
   if (do_pack) {
     ti.qual_reclaimed = c->qual_bytes - live_q;
     ti.val_reclaimed = c->val_bytes - live_v;
@@ -3562,16 +3567,6 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     c->qual_dead = dead_q;
     c->val_dead = dead_v;
   }
-  c->h_srp.swap(n_srp);
-  c->h_base.swap(n_base);
-  c->h_ndp.swap(n_ndp);
-  c->h_qlen.swap(n_qlen);
-  c->h_vlen.swap(n_vlen);
-  c->h_flags.swap(n_flags);
-  c->n_rows_loaded = NR2;
-  c->n_rows = c->h_srp[c->n_series];
-  c->max_series_rows = 0;
-  for (int64_t i = 0; i < c->n_series; i++) c->max_series_rows = std::max(c->max_series_rows, c->h_srp[i + 1] - c->h_srp[i]);
   // tsdbhip_load_cells' compaction errors: an entry whose row is gone is dropped
   if (!c->cmp_errs.empty() && evicted) {
     std::vector<tsdbhip_ctx::CmpErr> kept;
@@ -3580,21 +3575,9 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     c->cmp_errs.swap(kept);
   }
   std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
-  c->idx_fused = n_sus ? fused : false;
+  c->idx_fused = n_sus ? ip.fused : false;
   c->index_ms = t_index;
-  // what a load invalidates of the state that depends on the rows
-  c->none_tiles_ready = false;
-  c->acct_valid = false;
-  c->seqd_valid = false;
-  c->row_ser_valid = false;
-  c->n_grouped = -1;
-  c->mdp_valid = false;
-  c->ro_meta_valid = false;
-  c->lc_valid = false;
-  c->calc_valid = false;
-  c->ro_n = 0;       // (rollup and pre-aggregate cells belong to the batch they came from)
-  c->pg.cells = 0;
-  c->pg.qual_bytes = c->pg.value_bytes = 0;
+  invalidate_derived(c);
   const int rc = finish_classes(c);
   ti.rows_evicted = evicted;
   ti.series_emptied = emptied;
