@@ -928,6 +928,15 @@ int tsdbhip_debug_index(tsdbhip_ctx* ctx, uint32_t cnt[16], int* fused);
  * its ranks, a handed-back tile). */
 int tsdbhip_debug_sel_window(tsdbhip_ctx* ctx, int64_t* runs, int64_t* misses);
 
+/* Test hook (no reference counterpart): the route of the last tsdbhip_rollup_run on this
+ * single-device context.  out[0]: 1 when the streaming pass (k_rollup_fast) was launched, else 0;
+ * out[1]: the series it was launched over; out[2]: the series its first row class handed back
+ * (to the second class, or to the general kernel when there is none); out[3]: the series
+ * k_rollup_agg reduced -- every grouped series when there was no streaming pass.  A pure read of
+ * counters the run copied to the host with its first function's cell totals; all zeros before
+ * the first run.  A multi-device context answers TSDB_E_NOT_IMPLEMENTED. */
+int tsdbhip_debug_rollup(tsdbhip_ctx* ctx, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -495,6 +495,7 @@ struct tsdbhip_ctx {
   DevBuf hw_mark;                                      // k_hwin: a tile is on the redo list (one word a tile)
   int64_t tl_off[9] = {};                              // 3 cls + j (j < 3), 6: tl_other, 7 + cls: tl[cls][3]
   int64_t reg_launched = 0;                            // tiles the last query launched through k_fast's REG form
+  int64_t ro_route[4] = {0, 0, 0, 0};                  // the last tsdbhip_rollup_run's route (tsdbhip_debug_rollup)
   int reg_cls = 0;                                     // ... bit cls: that class's regular list went through it
   bool fast_used = false;
   HostBuf h_stage;   // collect(): the dense [G][K] values and flags, page-locked
@@ -3707,6 +3708,16 @@ extern "C" int tsdbhip_debug_sel_window(tsdbhip_ctx* c, int64_t* runs, int64_t* 
   CtxLock lk(c);
   if (runs) *runs = c->win_runs;
   if (misses) *misses = c->win_misses;
+  return 0;
+}
+
+// Test hook: the route of the last tsdbhip_rollup_run (streaming pass launched, its series, class
+// A's hand-backs, the series k_rollup_agg reduced).
+extern "C" int tsdbhip_debug_rollup(tsdbhip_ctx* c, int64_t out[4]) {
+  MD_REFUSE(c, "tsdbhip_debug_rollup");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  CtxLock lk(c);
+  if (out) std::memcpy(out, c->ro_route, sizeof(c->ro_route));
   return 0;
 }
 
@@ -7490,6 +7501,12 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
     if (rc) return rc;
   }
   const int64_t NS = c->n_series;
+  // tsdbhip_debug_rollup: the device counters of class A's hand-backs and of the general kernel's
+  // list (null without a streaming pass), read back with the first function's cell totals (no
+  // sync of their own; a run whose cells are then refused has still reported its route)
+  const int32_t* ro_na = nullptr;
+  const int32_t* ro_nagg = nullptr;
+  int32_t h_na = 0, h_nagg = 0;
   HIP_OK(c->ro_agg.ensure(std::max<int64_t>(1, 4 * NS * P.K) * 8));
   HIP_OK(c->ro_pres.ensure(std::max<int64_t>(1, NS * P.K)));
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
@@ -7522,6 +7539,10 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
                       rollup_fast_lds(P.K) <= 32 * 1024;
     const int32_t* list = nullptr;
     const int32_t* list_n = nullptr;
+    c->ro_route[0] = 0;
+    c->ro_route[1] = 0;
+    c->ro_route[2] = 0;
+    c->ro_route[3] = n;
     if (fast) {
       HIP_OK(c->r1a.ensure(n * 4));
       HIP_OK(c->r2.ensure(n * 4));
@@ -7547,9 +7568,13 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
         HIP_OK(launch_rollup_fast(fp, ap, qw, vl, c->stream));
         list = outs[cls];
         list_n = rn + cls;
+        if (!ro_na) ro_na = list_n;
       }
     }
     if (list) {
+      c->ro_route[0] = 1;
+      c->ro_route[1] = n;
+      ro_nagg = list_n;
       gp.tile_list = list;
       gp.tile_list_n = list_n;
       gp.n_launch = std::min<int64_t>(n, 16384);
@@ -7601,7 +7626,15 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
       { int rc_ = d2h_small(c, &last_v, rp.vsz + NK - 1, 4, c->stream); if (rc_) return rc_; }
     }
     { int rc_ = d2h_small(c, &err, c->err.p, 4, c->stream); if (rc_) return rc_; }
+    if (fi == 0 && ro_nagg) {
+      { int rc_ = d2h_small(c, &h_na, ro_na, 4, c->stream); if (rc_) return rc_; }
+      { int rc_ = d2h_small(c, &h_nagg, ro_nagg, 4, c->stream); if (rc_) return rc_; }
+    }
     { int rc_ = sync_small(c, c->stream); if (rc_) return rc_; }
+    if (fi == 0 && ro_nagg) {
+      c->ro_route[2] = h_na;
+      c->ro_route[3] = h_nagg;
+    }
     // an infinite bucket value trips AggregationIterator's Inf check (IllegalStateException)
     // in the NONE-aggregator pass; for a rollup it is addAggregatePoint's rejection
     if (err == TSDB_E_ILLEGAL_STATE) err = TSDB_E_ILLEGAL_ARGUMENT;

@@ -36,7 +36,7 @@ EXPORTS = [
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
-    "tsdbhip_debug_loaded", "tsdbhip_upsert",
+    "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -160,6 +160,7 @@ def lib():
         L.tsdbhip_debug_regular.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.tsdbhip_debug_index.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int)]
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
+        L.tsdbhip_debug_rollup.argtypes = [vp, C.c_void_p]
         L.tsdbhip_shard_bounds.argtypes = [C.POINTER(abi.Batch), C.c_int, C.c_int, C.c_void_p]
         L.tsdbhip_load_shard.argtypes = [vp, C.POINTER(abi.Batch), C.c_int, C.c_int64, C.c_int64]
         L.tsdbhip_synth_shard.argtypes = [vp, C.POINTER(abi.SynthSpec), C.c_int64, C.c_int64]
@@ -597,6 +598,13 @@ class Engine:
         runs, misses = C.c_int64(), C.c_int64()
         _check(lib().tsdbhip_debug_sel_window(self.ctx, C.byref(runs), C.byref(misses)))
         return runs.value, misses.value
+
+    def debug_rollup(self):
+        """Test hook: the last rollup_run's route -- (streaming pass launched 0 / 1, series it was
+        launched over, series its first row class handed back, series k_rollup_agg reduced)."""
+        out = np.zeros(4, np.int64)
+        _check(lib().tsdbhip_debug_rollup(self.ctx, out.ctypes.data))
+        return tuple(int(x) for x in out)
 
     # ---- rollup generation (tsdbhip_rollup_run) ----
     def rollup_run(self, interval: abi.RollupInterval, start_s: int, end_s: int,
