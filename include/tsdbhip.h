@@ -937,6 +937,18 @@ int tsdbhip_debug_sel_window(tsdbhip_ctx* ctx, int64_t* runs, int64_t* misses);
  * the first run.  A multi-device context answers TSDB_E_NOT_IMPLEMENTED. */
 int tsdbhip_debug_rollup(tsdbhip_ctx* ctx, int64_t out[4]);
 
+/* Test hook (no reference counterpart): the route of the last percentile / median downsampling
+ * run (p999 ... p50, ep*r3, ep*r7, median as the downsample function) on this single-device
+ * context.  out[0]: 1 when k_pct_rows was launched, else 0; out[1]: the KEYS code of the variant
+ * launched (0 extraction over doubles, 1 / 2 the 32-bit key kernel near the ends / at any rank,
+ * 5 / 6 the same over values alone, 13 / 14 the same six values a lane), -1 when none;
+ * out[2]: the series k_pct_rows handed back to k_pct; out[3]: the series with a bucket of more
+ * than 512 values, sent to the large-bucket pass; out[4]: that pass's waves (0 when it did not
+ * run); out[5]: its overflow region in values a wave (big_cap).  A pure read of values the run
+ * already held on the host; {0, -1, 0, 0, 0, 0} before the first run.  A multi-device context
+ * answers TSDB_E_NOT_IMPLEMENTED. */
+int tsdbhip_debug_pct(tsdbhip_ctx* ctx, int64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -496,6 +496,7 @@ struct tsdbhip_ctx {
   int64_t tl_off[9] = {};                              // 3 cls + j (j < 3), 6: tl_other, 7 + cls: tl[cls][3]
   int64_t reg_launched = 0;                            // tiles the last query launched through k_fast's REG form
   int64_t ro_route[4] = {0, 0, 0, 0};                  // the last tsdbhip_rollup_run's route (tsdbhip_debug_rollup)
+  int64_t pct_route[6] = {0, -1, 0, 0, 0, 0};          // the last percentile-downsampling run's route (tsdbhip_debug_pct)
   int reg_cls = 0;                                     // ... bit cls: that class's regular list went through it
   bool fast_used = false;
   HostBuf h_stage;   // collect(): the dense [G][K] values and flags, page-locked
@@ -3721,6 +3722,17 @@ extern "C" int tsdbhip_debug_rollup(tsdbhip_ctx* c, int64_t out[4]) {
   return 0;
 }
 
+// Test hook: the route of the last percentile-downsampling run (k_pct_rows launched, its KEYS
+// variant or -1, the series it handed back, the series sent to the large-bucket pass, that pass's
+// waves and its big_cap).
+extern "C" int tsdbhip_debug_pct(tsdbhip_ctx* c, int64_t out[6]) {
+  MD_REFUSE(c, "tsdbhip_debug_pct");
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  CtxLock lk(c);
+  if (out) std::memcpy(out, c->pct_route, sizeof(c->pct_route));
+  return 0;
+}
+
 // Test hook: the routes the last load's index took (class counts, k_index_short's hand-backs).
 extern "C" int tsdbhip_debug_index(tsdbhip_ctx* c, uint32_t cnt[16], int* fused) {
   MD_REFUSE(c, "tsdbhip_debug_index");
@@ -4522,6 +4534,8 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
     const bool keys = c->pct_vl == 4 && P.I == 3600000 && !opt_off(OPT_PCT_KEYS);
     const bool rows_path = P.mode == MODE_GRID && (near_end || keys) && P.I > 0 && 3600000 % P.I == 0 &&
                            P.B0 % P.I == 0 && pct_rows_supported(c->pct_qw, c->pct_vl) && !opt_off(OPT_PCT_ROWS);
+    int64_t route[6] = {0, -1, 0, 0, 0, 0};   // tsdbhip_debug_pct
+    std::memcpy(c->pct_route, route, sizeof(route));
     if (rows_path) {
       HIP_OK(c->redo2.ensure(std::max<int64_t>(1, c->n_series) * 4));
       HIP_OK(c->redo2_n.ensure(16));
@@ -4531,10 +4545,14 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
       rp.redo_n = c->redo2_n.as<int32_t>();
       rp.pct_vonly = keys && c->pct_vonly && !opt_off(OPT_PCT_VONLY);
       rp.pct_v6 = rp.pct_vonly && c->pct_v6 && !opt_off(OPT_PCT_V6);
-      HIP_OK(launch_pct_rows(rp, c->pct_qw, c->pct_vl, c->stream));
+      int variant = -1;
+      HIP_OK(launch_pct_rows(rp, c->pct_qw, c->pct_vl, c->stream, &variant));
       int32_t nback = 0;
       { int rc_ = d2h_small(c, &nback, c->redo2_n.p, 4, c->stream); if (rc_) return rc_; }
       { int rc_ = sync_small(c, c->stream); if (rc_) return rc_; }
+      route[0] = variant >= 0;
+      route[1] = variant;
+      route[2] = nback;
       gp.tile_list = c->redo2.as<int32_t>();
       gp.tile_list_n = c->redo2_n.as<int32_t>();
       HIP_OK(launch_pct(gp, 1, nback, c->stream));
@@ -4555,7 +4573,11 @@ int run_device(tsdbhip_ctx* c, const tsdbhip_query* q, const Plan& P, int64_t G,
       gp.big_cap = cap;
       gp.n_launch = nw;
       HIP_OK(launch_pct(gp, 2, nw, c->stream));
+      route[4] = nw;
+      route[5] = cap;
     }
+    route[3] = nbig;
+    std::memcpy(c->pct_route, route, sizeof(route));
     }
     if (!P.gsel && !P.ordered && !P.values_only)
       HIP_OK(launch_emit(gp, c->stream));   // else the caller takes the bucket values

@@ -771,7 +771,7 @@ static constexpr int PCT_CAP = 4096;   // values per bucket sorted in LDS; large
 // pass over redo_list (n = waves launched = p.n_launch)
 hipError_t launch_pct(const GridParams& p, int pass, int64_t n, hipStream_t s);
 bool pct_rows_supported(int qw, int vl);
-hipError_t launch_pct_rows(const GridParams& p, int qw, int vl, hipStream_t s);
+hipError_t launch_pct_rows(const GridParams& p, int qw, int vl, hipStream_t s, int* keys_out = nullptr);
 hipError_t launch_emit(const GridParams& p, hipStream_t s);
 // sum / avg downsampling in Java's order, one series per thread, into [series][K] (k_misc.hip)
 // sum / avg downsampling in Java's order, one row per thread, when every bucket lies inside one

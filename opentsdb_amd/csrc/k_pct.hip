@@ -18,9 +18,21 @@
 
 namespace tsdb {
 
+// a before b in Double.compareTo's order of non-NaN values (Collections.sort, the oracle's
+// cmp_double_total): numeric order, and -0.0 before 0.0 -- the two compare equal, and the sign
+// word of -0.0 is the smaller integer.  The key kernel's key32 and the radix select's f2key order
+// the zeros the same way, so every route puts the same zero on a rank.
+__device__ __forceinline__ bool lt_total(double a, double b) {
+  return a < b || (a == b && __double2hiint(a) < __double2hiint(b));
+}
+// the same value in that order: equal bits (no NaN here)
+__device__ __forceinline__ bool same_total(double a, double b) {
+  return __double_as_longlong(a) == __double_as_longlong(b);
+}
+
 // compare-exchange keeping (lo, hi); ties keep both values (multiset preserved)
 __device__ __forceinline__ void cx(double& a, double& b, bool up) {
-  const bool sw = up ? (b < a) : (a < b);
+  const bool sw = up ? lt_total(b, a) : lt_total(a, b);
   const double t = sw ? b : a;
   b = sw ? a : b;
   a = t;
@@ -42,7 +54,7 @@ __device__ __forceinline__ void sort512(double v[DPL]) {
           const bool up = (e & k) == 0;
           const bool lower = (e & jj) == 0;
           // the lower element of an ascending pair keeps the min
-          v[j] = (up == lower) ? ((o < v[j]) ? o : v[j]) : ((v[j] < o) ? o : v[j]);
+          v[j] = (up == lower) ? (lt_total(o, v[j]) ? o : v[j]) : (lt_total(v[j], o) ? o : v[j]);
         }
       } else {
 #pragma unroll
@@ -130,6 +142,9 @@ __device__ __forceinline__ double wave_ext_f64(double x) {
 // step; returns the last two extracted (e_k, e_{k-1}).  Used when the requested order
 // statistics lie within 24 of either end (p95..p999 of 1 h @10 s buckets: 1..19 steps)
 // instead of a 512-element bitonic sort; the values are the same order statistics.
+// The order is lt_total's: fmax / fmin and == take -0.0 and 0.0 for one value, so when the
+// extreme is a zero (wave-uniform) its sign is settled from the candidates -- 0.0 is the larger --
+// and the occurrence removed is the one with the extreme's own bits.
 template <bool MAX>
 __device__ __forceinline__ void extract_k(double v[DPL], int k, double& ek, double& ek1) {
   const int lane = lane_id();
@@ -139,14 +154,24 @@ __device__ __forceinline__ void extract_k(double v[DPL], int k, double& ek, doub
     double m = v[0];
 #pragma unroll
     for (int j = 1; j < DPL; j++) m = MAX ? fmax(m, v[j]) : fmin(m, v[j]);
-    const double w = wave_ext_f64<MAX>(m);
-    const uint64_t holders = __ballot(m == w);
+    double w = wave_ext_f64<MAX>(m);
+    bool hold = m == w;
+    if (w == 0.0) {
+      bool outer = false;   // a zero of the outer sign: 0.0 for the maximum, -0.0 for the minimum
+#pragma unroll
+      for (int j = 0; j < DPL; j++) outer = outer || same_total(v[j], MAX ? 0.0 : -0.0);
+      w = ((__ballot(outer) != 0) == MAX) ? 0.0 : -0.0;
+      hold = false;
+#pragma unroll
+      for (int j = 0; j < DPL; j++) hold = hold || same_total(v[j], w);
+    }
+    const uint64_t holders = __ballot(hold);
     const int first = __ffsll((long long)holders) - 1;
     if (lane == first) {
       bool done = false;
 #pragma unroll
       for (int j = 0; j < DPL; j++) {
-        if (!done && v[j] == w) { v[j] = gone; done = true; }
+        if (!done && same_total(v[j], w)) { v[j] = gone; done = true; }
       }
     }
     ek1 = ek;
@@ -868,7 +893,8 @@ __device__ __forceinline__ int wave_min_dpp(int x) {
 }
 
 // k-th largest (MAX) / smallest value of the multiset {val[j] : keep bit j}, and the
-// (k-1)-th; one occurrence removed per step (ties kept as a multiset)
+// (k-1)-th; one occurrence removed per step (ties kept as a multiset); lt_total's order, the
+// sign of a zero extreme settled as in extract_k
 template <bool MAX>
 __device__ __forceinline__ void extract_masked(const double val[DPL], uint32_t keep, int k, double& ek, double& ek1) {
   const int lane = lane_id();
@@ -881,13 +907,23 @@ __device__ __forceinline__ void extract_masked(const double val[DPL], uint32_t k
       const double c = MAX ? fmax(m, val[j]) : fmin(m, val[j]);
       m = ((keep >> j) & 1) ? c : m;
     }
-    const double w = wave_ext_f64<MAX>(m);
-    const uint64_t holders = __ballot(keep != 0 && m == w);
+    double w = wave_ext_f64<MAX>(m);
+    bool hold = keep != 0 && m == w;
+    if (w == 0.0) {
+      bool outer = false;   // a kept zero of the outer sign: 0.0 for the maximum, -0.0 for the minimum
+#pragma unroll
+      for (int j = 0; j < DPL; j++) outer = outer || (((keep >> j) & 1) && same_total(val[j], MAX ? 0.0 : -0.0));
+      w = ((__ballot(outer) != 0) == MAX) ? 0.0 : -0.0;
+      hold = false;
+#pragma unroll
+      for (int j = 0; j < DPL; j++) hold = hold || (((keep >> j) & 1) && same_total(val[j], w));
+    }
+    const uint64_t holders = __ballot(hold);
     const int first = __ffsll((long long)holders) - 1;
     if (lane == first) {
       uint32_t hit = 0;
 #pragma unroll
-      for (int j = DPL - 1; j >= 0; j--) if (((keep >> j) & 1) && val[j] == w) hit = 1u << j;
+      for (int j = DPL - 1; j >= 0; j--) if (((keep >> j) & 1) && same_total(val[j], w)) hit = 1u << j;
       keep &= ~hit;
     }
     ek1 = ek;
@@ -2440,7 +2476,9 @@ hipError_t launch_sel_seg(const SelParams& p, hipStream_t s, int64_t maxn) {
   return hipGetLastError();
 }
 
-hipError_t launch_pct_rows(const GridParams& p, int qw, int vl, hipStream_t s) {
+// *keys_out: the KEYS code of the variant launched (-1 = none)
+hipError_t launch_pct_rows(const GridParams& p, int qw, int vl, hipStream_t s, int* keys_out) {
+  if (keys_out) *keys_out = -1;
   if (p.n_series == 0) return hipSuccess;
   const dim3 grid((unsigned)((p.n_series + 3) / 4)), block(256);
   // ring depth: 3 rows for the general kernel; 2 for the key kernel (config 5 1h-p99: 18.1 /
@@ -2452,23 +2490,25 @@ hipError_t launch_pct_rows(const GridParams& p, int qw, int vl, hipStream_t s) {
   const bool mid = p.sel_fn == TSDB_AGG_MEDIAN || sel_i >= 4;   // median, p75, p50 (and their ep* forms)
 #define PCT_ROWS_CASE(Q, V)                                                                                  \
   if (qw == Q && vl == V) {                                                                                \
+    int kc = 0;                                                                                            \
     if (V == 4 && keys && p.pct_vonly && p.pct_v6) {                                                       \
+      kc = mid ? 14 : 13;                                                                                  \
       if (mid) hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 14>), grid, block, 0, s, p);                       \
       else hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 13>), grid, block, 0, s, p);                            \
-      return hipGetLastError();                                                                            \
-    }                                                                                                      \
-    if (V == 4 && keys && p.pct_vonly) {                                                                   \
+    } else if (V == 4 && keys && p.pct_vonly) {                                                            \
+      kc = mid ? 6 : 5;                                                                                    \
       if (mid) hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 6>), grid, block, 0, s, p);                        \
       else hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 5>), grid, block, 0, s, p);                             \
-      return hipGetLastError();                                                                            \
-    }                                                                                                      \
-    if (V == 4 && keys) {                                                                                  \
+    } else if (V == 4 && keys) {                                                                           \
+      kc = mid ? 2 : 1;                                                                                    \
       if (mid) hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 2>), grid, block, 0, s, p);                        \
       else hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 1>), grid, block, 0, s, p);                             \
-      return hipGetLastError();                                                                            \
+    } else if (D == 2) {                                                                                   \
+      hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 0>), grid, block, 0, s, p);                                  \
+    } else {                                                                                               \
+      hipLaunchKernelGGL((k_pct_rows<Q, V, 3, 0>), grid, block, 0, s, p);                                  \
     }                                                                                                      \
-    if (D == 2) hipLaunchKernelGGL((k_pct_rows<Q, V, 2, 0>), grid, block, 0, s, p);                        \
-    else hipLaunchKernelGGL((k_pct_rows<Q, V, 3, 0>), grid, block, 0, s, p);                               \
+    if (keys_out) *keys_out = kc;                                                                          \
     return hipGetLastError();                                                                              \
   }
   PCT_ROWS_CASE(2, 1) PCT_ROWS_CASE(2, 2) PCT_ROWS_CASE(2, 4) PCT_ROWS_CASE(2, 8)

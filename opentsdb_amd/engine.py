@@ -36,7 +36,7 @@ EXPORTS = [
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
-    "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup",
+    "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -161,6 +161,7 @@ def lib():
         L.tsdbhip_debug_index.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int)]
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_rollup.argtypes = [vp, C.c_void_p]
+        L.tsdbhip_debug_pct.argtypes = [vp, C.c_void_p]
         L.tsdbhip_shard_bounds.argtypes = [C.POINTER(abi.Batch), C.c_int, C.c_int, C.c_void_p]
         L.tsdbhip_load_shard.argtypes = [vp, C.POINTER(abi.Batch), C.c_int, C.c_int64, C.c_int64]
         L.tsdbhip_synth_shard.argtypes = [vp, C.POINTER(abi.SynthSpec), C.c_int64, C.c_int64]
@@ -604,6 +605,14 @@ class Engine:
         launched over, series its first row class handed back, series k_rollup_agg reduced)."""
         out = np.zeros(4, np.int64)
         _check(lib().tsdbhip_debug_rollup(self.ctx, out.ctypes.data))
+        return tuple(int(x) for x in out)
+
+    def debug_pct(self):
+        """Test hook: the last percentile-downsampling run's route -- (k_pct_rows launched 0 / 1,
+        its KEYS variant or -1, series it handed back, series sent to the large-bucket pass, that
+        pass's waves, its big_cap)."""
+        out = np.zeros(6, np.int64)
+        _check(lib().tsdbhip_debug_pct(self.ctx, out.ctypes.data))
         return tuple(int(x) for x in out)
 
     # ---- rollup generation (tsdbhip_rollup_run) ----
