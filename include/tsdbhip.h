@@ -296,7 +296,8 @@ int tsdbhip_append(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* 
  * last, or onto a series with zero rows.  A series' delta rows may come in any order; rows of the
  * delta that share (series, base) are merged first, as tsdbhip_load merges them.  This is what
  * late datapoints for a closed hour, the compaction queue's rewrite of a closed hour's row, a
- * fix_duplicates repair and a collector's back-fill need.  Rows cannot be removed (tsdbhip_trim).
+ * fix_duplicates repair and a collector's back-fill need.  Rows are removed by tsdbhip_remove
+ * (and, at a series' old end, by tsdbhip_trim).
  * Afterwards the context answers every entry point as a fresh tsdbhip_load of the merged batch,
  * followed by the tsdbhip_regroup that reproduces the present ids, would, bit for bit, with
  * tsdbhip_append's exceptions: tsdbhip_debug_index and timing.index_ms describe this call's
@@ -361,6 +362,59 @@ typedef struct {
 } tsdbhip_trim_info;
 #define TSDB_TRIM_NO_PACK (-1)
 int tsdbhip_trim(tsdbhip_ctx* ctx, int64_t cutoff_s, int32_t pack_dead_pct, tsdbhip_trim_info* info /* may be NULL */);
+/* Rows removed from anywhere in the resident batch, and row-less series retired:
+ * what a delete query (TsdbQuery.setDelete, SaltScanner.processRow's DeleteRequest per scanned
+ * row), fsck --fix, scan --delete and an HBase TTL do to the store.  Range k removes the rows of
+ * series ranges[k].series_index -- a batch index in the numbering BEFORE the call -- whose base
+ * time lies in [from_s, to_s): a single row is [b, b + 1), a whole series [0, 2^32).  A series may
+ * have any number of ranges, in any order, overlapping or repeated, and ranges apply to visible
+ * and to excluded series alike.  A range that covers no row is legal (ranges_empty counts them),
+ * from_s == to_s included.  The call is idempotent, and remove(R1) then remove(R2) equals
+ * remove(R1 u R2).
+ * Without TSDB_REMOVE_DROP_EMPTY the series set, batch order and every group id are unchanged, as
+ * after tsdbhip_trim; series_emptied counts the series this call left without rows and
+ * new_index[i] = i.  With it every series that has no row after the removal is retired -- those
+ * emptied by earlier trims and those that never had a row included -- and the batch is renumbered:
+ * the remaining series keep their relative order, their group ids and their exclusions,
+ * N' = N - series_dropped, new_index[i] is the new batch index or -1 for a retired series, and
+ * from then on tsdbhip_regroup takes N' ids and series_index of tsdbhip_append / tsdbhip_upsert is
+ * in the new numbering.  n_ranges == 0 with the flag retires what trims emptied.
+ * Afterwards the context answers every entry point as a fresh tsdbhip_load of the remaining
+ * batch, followed by the tsdbhip_regroup that reproduces the remaining series' present ids,
+ * would, bit for bit (n_groups shrinks when the highest id's series are all retired) -- with
+ * tsdbhip_trim's and tsdbhip_upsert's exceptions: tsdbhip_debug_index and timing.index_ms describe
+ * the suspects' re-index pass (zero rows when none was suspect), cells of an earlier
+ * tsdbhip_rollup_run / tsdbhip_preagg_run are dropped, and a tsdbhip_load_cells compaction error
+ * whose row is removed is dropped (one on a kept row is renumbered with its series).  A call that
+ * removes nothing, retires nothing and does not pack changes nothing of the batch -- with one
+ * exception: a row whose compaction failed is never resident, so its error is dropped whenever a
+ * range covers its (series, base), and the queries that raised it answer from then on.
+ * A removed row may have caused a later row's ROW_UNSORTED: kept rows that carry the flag and lie
+ * after their series' earliest removed row are indexed again and their series walked, as
+ * tsdbhip_trim treats its suspects (rows_reindexed).  A removal cannot make a row gain the flag.
+ * pack_dead_pct is tsdbhip_trim's, TSDB_TRIM_NO_PACK included: without a pack the removed rows'
+ * aligned lengths are added to the dead bytes wherever the rows sat; with one the blobs are re-laid
+ * by tsdbhip_trim's pack stage.
+ * TSDB_E_ILLEGAL_ARGUMENT: a null context, pack_dead_pct > 100, n_ranges < 0, null ranges with
+ * n_ranges > 0, a series_index outside [0, N), from_s < 0, from_s > to_s, unknown flag bits.
+ * TSDB_E_NOT_IMPLEMENTED: a multi-device context, a rollup batch, a shard load, 2^31 - 1 rows or
+ * more.  TSDB_E_NOMEM: the fresh blobs do not fit beside the old ones (retry with
+ * TSDB_TRIM_NO_PACK).  An error leaves the resident batch as it was. */
+typedef struct {
+  int64_t series_index;   /* batch index, in the numbering BEFORE the call */
+  int64_t from_s, to_s;   /* the series' rows with from_s <= base < to_s go */
+} tsdbhip_remove_range;
+#define TSDB_REMOVE_DROP_EMPTY 1u
+typedef struct {
+  int64_t rows_removed, series_emptied, series_dropped, rows_reindexed, ranges_empty;
+  uint64_t qual_capacity, val_capacity;     /* as tsdbhip_trim_info */
+  uint64_t qual_dead, val_dead;
+  uint64_t qual_reclaimed, val_reclaimed;
+  int32_t packed;
+} tsdbhip_remove_info;
+int tsdbhip_remove(tsdbhip_ctx* ctx, const tsdbhip_remove_range* ranges, int64_t n_ranges, uint32_t flags,
+                   int32_t pack_dead_pct, int64_t* new_index /* N entries, may be NULL */,
+                   tsdbhip_remove_info* info /* may be NULL */);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:

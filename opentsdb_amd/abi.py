@@ -262,6 +262,36 @@ class TrimInfo(C.Structure):
     ]
 
 
+REMOVE_DROP_EMPTY = 1    # tsdbhip.h TSDB_REMOVE_DROP_EMPTY: tsdbhip_remove retires the row-less series
+
+
+class RemoveRange(C.Structure):
+    """tsdbhip_remove_range: the rows of one series with from_s <= base time < to_s."""
+    _fields_ = [
+        ("series_index", C.c_int64),
+        ("from_s", C.c_int64),
+        ("to_s", C.c_int64),
+    ]
+
+
+class RemoveInfo(C.Structure):
+    """tsdbhip_remove_info: what a tsdbhip_remove did to the resident batch."""
+    _fields_ = [
+        ("rows_removed", C.c_int64),
+        ("series_emptied", C.c_int64),
+        ("series_dropped", C.c_int64),
+        ("rows_reindexed", C.c_int64),
+        ("ranges_empty", C.c_int64),
+        ("qual_capacity", C.c_uint64),
+        ("val_capacity", C.c_uint64),
+        ("qual_dead", C.c_uint64),
+        ("val_dead", C.c_uint64),
+        ("qual_reclaimed", C.c_uint64),
+        ("val_reclaimed", C.c_uint64),
+        ("packed", C.c_int32),
+    ]
+
+
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,
               ds_all: bool = False, rate: bool = False, counter: bool = False,

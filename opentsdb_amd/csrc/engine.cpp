@@ -423,6 +423,10 @@ struct tsdbhip_ctx {
   // descriptors and RegRows; the packed layout's row offsets
   DevBuf tr_skip, tr_list, tr_ser, tr_rows, tr_reg, tr_qdst, tr_vdst;
   HostBuf tr_stage;                    // ... page-locked (skips, then the suspect rows, then their series)
+  // tsdbhip_remove: the ranges, the rows [lo, hi) each covers, the difference array over the rows
+  // (then the ranges covering each), the kept rows before each row
+  DevBuf rm_ranges, rm_lohi, rm_diff, rm_pos;
+  HostBuf rm_stage;                    // ... page-locked (the ranges, their rows, then series_row_ptr and the group keys)
   std::vector<int64_t> h_srp;          // [n_series+1]
   std::vector<uint32_t> h_base;        // [n_rows]
   std::vector<uint32_t> h_ndp;         // [n_rows]
@@ -872,7 +876,7 @@ static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
                     &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
-                    &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S})
+                    &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S, &c->rm_ranges, &c->rm_lohi, &c->rm_diff, &c->rm_pos})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -947,6 +951,7 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   c->rg_stage.release();
   c->rg_rows.release();
   c->ap_stage.release();
+  c->rm_stage.release();
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
   for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
@@ -2617,7 +2622,7 @@ extern "C" int tsdbhip_synth_shard(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp,
 
 // ===========================================================================
 // in-place edits of the resident batch: tsdbhip_regroup, tsdbhip_append, tsdbhip_upsert,
-// tsdbhip_trim.  One skeleton: validate, allocate, queue, download, commit,
+// tsdbhip_trim, tsdbhip_remove.  One skeleton: validate, allocate, queue, download, commit,
 // invalidate_derived, finish_classes -- the resident batch stays as it is until the commit.
 // ===========================================================================
 
@@ -3378,6 +3383,80 @@ extern "C" int tsdbhip_upsert(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   return 0;
 }
 
+// The pack stage that tsdbhip_trim and tsdbhip_remove share: the cells of every
+// gathered row copied into fresh blobs in descriptor order, 16-byte aligned with zero padding.
+// ensure allocates the fresh blobs beside the resident ones before anything is queued; queue runs
+// the two aligned-length scans, k_trim_pack<KIND> and k_trim_offsets over rows2; settle, after
+// Mirrors::commit, swaps the blobs in (val2 is released when no kept row needs it) or, without a
+// pack, books the dead bytes.
+struct BlobPack {
+  bool on = false, v2 = false;
+  uint64_t live_q = 0, live_v = 0;   // the kept rows' aligned bytes
+  BlobHold hold;
+  int ensure(tsdbhip_ctx* c, const std::string& fn, const char* nomem_hint, int64_t nr2, bool need_v2_after) {
+    if (!on) return 0;
+    auto nomem = [&](hipError_t e) { return edit_nomem(fn, e, nomem_hint); };
+    v2 = c->val2.p != nullptr && need_v2_after;
+    if (v2 && c->val2.n < c->qual_bytes)
+      return fail(TSDB_E_HIP, fn + ": the int16 value copy is shorter than the qualifier blob (internal)");
+    hipError_t he;
+    if ((he = hold.q.ensure(grown(live_q + BLOB_SLACK))) != hipSuccess) return nomem(he);
+    if ((he = hold.v.ensure(grown(live_v + BLOB_SLACK))) != hipSuccess) return nomem(he);
+    if (v2 && (he = hold.v2.ensure(hold.q.n)) != hipSuccess) return nomem(he);   // (val2 lives at qualifier offsets)
+    HIP_OK(c->tr_qdst.ensure((size_t)(nr2 + 1) * 8));
+    HIP_OK(c->tr_vdst.ensure((size_t)(nr2 + 1) * 8));
+    return 0;
+  }
+  int queue(tsdbhip_ctx* c, RowDesc* rows_new, int64_t nr2) {
+    if (!on) return 0;
+    HIP_OK(trim_pack_scan(rows_new, nr2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp, &c->rg_tmp_bytes,
+                          c->stream));
+    // (the slack past the packed end, and the reserve, read as zeros)
+    HIP_OK(hipMemsetAsync(hold.q.as<uint8_t>() + live_q, 0, hold.q.n - live_q, c->stream));
+    HIP_OK(hipMemsetAsync(hold.v.as<uint8_t>() + live_v, 0, hold.v.n - live_v, c->stream));
+    if (v2) HIP_OK(hipMemsetAsync(hold.v2.as<uint8_t>() + live_q, 0, hold.v2.n - live_q, c->stream));
+    TrimPackParams pp{};
+    pp.rows = rows_new;
+    pp.n_rows = nr2;
+    pp.qdst = c->tr_qdst.as<uint64_t>();
+    pp.vdst = c->tr_vdst.as<uint64_t>();
+    pp.q_total = live_q;
+    pp.v_total = live_v;
+    pp.qual = c->qual.as<uint8_t>();
+    pp.val = c->val.as<uint8_t>();
+    pp.val2 = v2 ? c->val2.as<uint8_t>() : nullptr;
+    pp.qual_new = hold.q.as<uint8_t>();
+    pp.val_new = hold.v.as<uint8_t>();
+    pp.val2_new = v2 ? hold.v2.as<uint8_t>() : nullptr;
+    HIP_OK(launch_trim_pack(pp, c->stream));
+    HIP_OK(launch_trim_offsets(rows_new, pp.qdst, pp.vdst, nr2, c->stream));
+    return 0;
+  }
+  // dead_q / dead_v: the dead bytes after the call when it does not pack
+  template <class Info> void settle(tsdbhip_ctx* c, Info* ti, uint64_t dead_q, uint64_t dead_v) {
+    if (!on) {
+      c->qual_dead = dead_q;
+      c->val_dead = dead_v;
+      return;
+    }
+    ti->qual_reclaimed = c->qual_bytes - live_q;
+    ti->val_reclaimed = c->val_bytes - live_v;
+    ti->packed = 1;
+    std::swap(c->qual, hold.q);
+    std::swap(c->val, hold.v);
+    if (v2) std::swap(c->val2, hold.v2);
+    else c->val2.release();   // (no kept row reads an int16 copy: a load of this batch would have none)
+    c->qual_bytes = live_q;
+    c->val_bytes = live_v;
+    c->qual_dead = c->val_dead = 0;
+  }
+};
+// does the call pack?  dead: the dead bytes of both blobs after it
+static bool pack_wanted(const tsdbhip_ctx* c, int32_t pack_dead_pct, uint64_t dead) {
+  const uint64_t used = c->qual_bytes + c->val_bytes;
+  return pack_dead_pct >= 0 && (unsigned __int128)dead * 100 >= (unsigned __int128)used * (uint64_t)pack_dead_pct;
+}
+
 // Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
 // bytes.  The descriptors are gathered with a per-series skip; kept rows whose
 // ROW_UNSORTED an evicted row may have caused are indexed again in an array of their own
@@ -3431,9 +3510,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   }
   const int64_t NR2 = NR - evicted;
   const uint64_t dead_q = c->qual_dead + ev_q, dead_v = c->val_dead + ev_v;
-  const uint64_t used = c->qual_bytes + c->val_bytes;
-  const bool do_pack =
-      pack_dead_pct >= 0 && (unsigned __int128)(dead_q + dead_v) * 100 >= (unsigned __int128)used * (uint64_t)pack_dead_pct;
+  const bool do_pack = pack_wanted(c, pack_dead_pct, dead_q + dead_v);
   if (evicted == 0 && !do_pack) { fill_info(); return 0; }   // (nothing changes)
   // the suspect rows, as positions in the gathered array, and their series
   int64_t* const sus = skip + N;
@@ -3447,22 +3524,13 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     if (n_sus > before) sus_ser[n_ser++] = (int32_t)i;
   }
   // ---- allocations: nothing of the resident batch is released before the commit ----
-  BlobHold hold;
   const std::string fn = "tsdbhip_trim";
   const char* const nomem_hint = "the packed blobs do not fit beside the resident ones (retry with TSDB_TRIM_NO_PACK)";
-  auto nomem = [&](hipError_t e) { return edit_nomem(fn, e, nomem_hint); };
-  const bool had_val2 = c->val2.p != nullptr;
-  const bool pack_v2 = do_pack && had_val2 && need_v2_after;
-  if (pack_v2 && c->val2.n < c->qual_bytes)
-    return fail(TSDB_E_HIP, "tsdbhip_trim: the int16 value copy is shorter than the qualifier blob (internal)");
-  hipError_t he;
-  if (do_pack) {
-    if ((he = hold.q.ensure(grown(live_q + BLOB_SLACK))) != hipSuccess) return nomem(he);
-    if ((he = hold.v.ensure(grown(live_v + BLOB_SLACK))) != hipSuccess) return nomem(he);
-    if (pack_v2 && (he = hold.v2.ensure(hold.q.n)) != hipSuccess) return nomem(he);   // (val2 lives at qualifier offsets)
-    HIP_OK(c->tr_qdst.ensure((size_t)(NR2 + 1) * 8));
-    HIP_OK(c->tr_vdst.ensure((size_t)(NR2 + 1) * 8));
-  }
+  BlobPack pack;
+  pack.on = do_pack;
+  pack.live_q = live_q;
+  pack.live_v = live_v;
+  if (const int rc = pack.ensure(c, fn, nomem_hint, NR2, need_v2_after)) return rc;
   HIP_OK(c->tr_skip.ensure((size_t)N * 8));
   HIP_OK(c->rows2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
   HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RegRow)));
@@ -3518,29 +3586,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
     (void)hipEventElapsedTime(&t_index, c->ev[2], c->ev[3]);
   }
   HIP_OK(tr.mark(2));
-  if (do_pack) {
-    HIP_OK(trim_pack_scan(tp.rows_new, NR2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp, &c->rg_tmp_bytes,
-                          c->stream));
-    // (the slack past the packed end, and the reserve, read as zeros)
-    HIP_OK(hipMemsetAsync(hold.q.as<uint8_t>() + live_q, 0, hold.q.n - live_q, c->stream));
-    HIP_OK(hipMemsetAsync(hold.v.as<uint8_t>() + live_v, 0, hold.v.n - live_v, c->stream));
-    if (pack_v2) HIP_OK(hipMemsetAsync(hold.v2.as<uint8_t>() + live_q, 0, hold.v2.n - live_q, c->stream));
-    TrimPackParams pp{};
-    pp.rows = tp.rows_new;
-    pp.n_rows = NR2;
-    pp.qdst = c->tr_qdst.as<uint64_t>();
-    pp.vdst = c->tr_vdst.as<uint64_t>();
-    pp.q_total = live_q;
-    pp.v_total = live_v;
-    pp.qual = c->qual.as<uint8_t>();
-    pp.val = c->val.as<uint8_t>();
-    pp.val2 = pack_v2 ? c->val2.as<uint8_t>() : nullptr;
-    pp.qual_new = hold.q.as<uint8_t>();
-    pp.val_new = hold.v.as<uint8_t>();
-    pp.val2_new = pack_v2 ? hold.v2.as<uint8_t>() : nullptr;
-    HIP_OK(launch_trim_pack(pp, c->stream));
-    HIP_OK(launch_trim_offsets(tp.rows_new, pp.qdst, pp.vdst, NR2, c->stream));
-  }
+  if (const int rc = pack.queue(c, tp.rows_new, NR2)) return rc;
   HIP_OK(tr.mark(3));
   // host mirrors from a download of the final descriptors
   HIP_OK(m.download(c, NR2));
@@ -3554,21 +3600,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   // ---- commit: from here on the context holds the trimmed batch; the series' order, groups and
   // exclusions stay ----
   m.commit(c, nullptr);
-  if (do_pack) {
-    ti.qual_reclaimed = c->qual_bytes - live_q;
-    ti.val_reclaimed = c->val_bytes - live_v;
-    ti.packed = 1;
-    std::swap(c->qual, hold.q);
-    std::swap(c->val, hold.v);
-    if (pack_v2) std::swap(c->val2, hold.v2);
-    else c->val2.release();   // (no kept row reads an int16 copy: a load of this batch would have none)
-    c->qual_bytes = live_q;
-    c->val_bytes = live_v;
-    c->qual_dead = c->val_dead = 0;
-  } else {
-    c->qual_dead = dead_q;
-    c->val_dead = dead_v;
-  }
+  pack.settle(c, &ti, dead_q, dead_v);
   // tsdbhip_load_cells' compaction errors: an entry whose row is gone is dropped
   if (!c->cmp_errs.empty() && evicted) {
     std::vector<tsdbhip_ctx::CmpErr> kept;
@@ -3584,6 +3616,325 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   ti.rows_evicted = evicted;
   ti.series_emptied = emptied;
   ti.rows_reindexed = n_sus;
+  fill_info();
+  return rc;
+}
+
+// Rows removed from anywhere in the resident batch by (series, base-time range), and row-less
+// series retired on demand.  Which rows a range covers is found on the device
+// (k_remove_mark); the host walks the touched series only, for the dead bytes, the suspects and the
+// new series_row_ptr; two scans over the rows give each kept row's place and k_remove_gather
+// builds the descriptors.  The suspects and the pack are tsdbhip_trim's.  With
+// TSDB_REMOVE_DROP_EMPTY the series are renumbered through SeriesOrder, as tsdbhip_append renumbers
+// them for a grown series count.  Everything is validated before anything is allocated or queued;
+// the resident batch stays as it is until the commit.
+extern "C" int tsdbhip_remove(tsdbhip_ctx* c, const tsdbhip_remove_range* ranges, int64_t n_ranges, uint32_t flags,
+                              int32_t pack_dead_pct, int64_t* new_index, tsdbhip_remove_info* info) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  if (pack_dead_pct > 100) return fail(TSDB_E_ILLEGAL_ARGUMENT, "pack_dead_pct above 100");
+  if (n_ranges < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_ranges below 0");
+  if (n_ranges > 0 && !ranges) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ranges");
+  if (flags & ~(uint32_t)TSDB_REMOVE_DROP_EMPTY) return fail(TSDB_E_ILLEGAL_ARGUMENT, "unknown flag bits");
+  MD_REFUSE(c, "tsdbhip_remove");
+  CtxLock lk(c);
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_remove over a rollup batch (tsdbhip_load_rollup)");
+  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
+  if (!c->regroup_ok && (N > 0 || n_ranges > 0))
+    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_remove needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                        "tsdbhip_synth (a shard's groups are numbered globally)");
+  if (NR >= INT32_MAX) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_remove over 2^31 - 1 rows or more");
+  for (int64_t k = 0; k < n_ranges; k++) {
+    const tsdbhip_remove_range& g = ranges[k];
+    if (g.series_index < 0 || g.series_index >= N)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT,
+                  "series_index " + std::to_string(g.series_index) + " outside [0, " + std::to_string(N) + ")");
+    if (g.from_s < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "from_s below 0");
+    if (g.from_s > g.to_s) return fail(TSDB_E_ILLEGAL_ARGUMENT, "from_s above to_s");
+  }
+  const bool drop = (flags & TSDB_REMOVE_DROP_EMPTY) != 0;
+  tsdbhip_remove_info ri{};
+  auto fill_info = [&]() {
+    fill_blob_info(&ri, c);
+    if (info) *info = ri;
+  };
+  auto identity = [&]() {
+    for (int64_t b = 0; new_index && b < N; b++) new_index[b] = b;
+  };
+  if (N == 0) { ri.ranges_empty = n_ranges; fill_info(); return 0; }
+  HIP_OK(hipSetDevice(c->device));
+  const std::string fn = "tsdbhip_remove";
+  const char* const nomem_hint = "the packed blobs do not fit beside the resident ones (retry with TSDB_TRIM_NO_PACK)";
+  std::vector<int32_t> pos(N);   // batch index -> current resident position
+  for (int64_t i = 0; i < N; i++) pos[c->h_orig[i]] = (int32_t)i;
+  // ---- which rows each range covers: found on the device, read back at 16 B a range ----
+  StageTrace<7> tr;
+  HIP_OK(tr.begin(c->stream));
+  // the page-locked staging: the ranges, their rows, then the new series_row_ptr and the group keys
+  const size_t st_ranges = 0, st_lohi = st_ranges + (size_t)n_ranges * sizeof(RemoveRange);
+  const size_t st_srp = st_lohi + (size_t)n_ranges * 16, st_gid = st_srp + (size_t)(N + 1) * 8;
+  HIP_OK(c->rm_stage.ensure(st_gid + (size_t)N * 4));
+  uint8_t* const stage = reinterpret_cast<uint8_t*>(c->rm_stage.p);
+  RemoveRange* const h_ranges = reinterpret_cast<RemoveRange*>(stage + st_ranges);
+  const int64_t* const h_lohi = reinterpret_cast<const int64_t*>(stage + st_lohi);
+  int64_t* const st_n_srp = reinterpret_cast<int64_t*>(stage + st_srp);
+  int32_t* const st_key = reinterpret_cast<int32_t*>(stage + st_gid);
+  HIP_OK(c->rm_diff.ensure((size_t)(NR + 1) * 4));
+  HIP_OK(c->rm_pos.ensure((size_t)(NR + 1) * 4));
+  HIP_OK(tr.mark(0));
+  HIP_OK(hipMemsetAsync(c->rm_diff.p, 0, (size_t)(NR + 1) * 4, c->stream));
+  if (n_ranges) {
+    HIP_OK(c->rm_ranges.ensure((size_t)n_ranges * sizeof(RemoveRange)));
+    HIP_OK(c->rm_lohi.ensure((size_t)n_ranges * 16));
+    for (int64_t k = 0; k < n_ranges; k++) {
+      h_ranges[k].from_s = ranges[k].from_s;
+      h_ranges[k].to_s = ranges[k].to_s;
+      h_ranges[k].series = pos[ranges[k].series_index];
+      h_ranges[k].pad = 0;
+    }
+    HIP_OK(hipMemcpyAsync(c->rm_ranges.p, h_ranges, (size_t)n_ranges * sizeof(RemoveRange), hipMemcpyHostToDevice, c->stream));
+    RemoveMarkParams mp{};
+    mp.ranges = c->rm_ranges.as<RemoveRange>();
+    mp.n_ranges = n_ranges;
+    mp.srp_old = c->srp.as<int64_t>();
+    mp.rows_old = c->rows.as<RowDesc>();
+    mp.lohi = c->rm_lohi.as<int64_t>();
+    mp.diff = c->rm_diff.as<int32_t>();
+    HIP_OK(launch_remove_mark(mp, c->stream));
+    HIP_OK(hipMemcpyAsync(stage + st_lohi, c->rm_lohi.p, (size_t)n_ranges * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+  }
+  HIP_OK(tr.mark(1));
+  // ---- the host's walk over the touched series: the ranges that cover a row, by (series, first
+  // row), merged where they overlap ----
+  std::vector<int64_t> hit;
+  for (int64_t k = 0; k < n_ranges; k++) {
+    if (h_lohi[2 * k] < h_lohi[2 * k + 1]) hit.push_back(k);
+    else ri.ranges_empty++;
+  }
+  std::sort(hit.begin(), hit.end(), [&](int64_t x, int64_t y) {   // (rows are numbered series by series)
+    return h_lohi[2 * x] != h_lohi[2 * y] ? h_lohi[2 * x] < h_lohi[2 * y] : h_lohi[2 * x + 1] < h_lohi[2 * y + 1];
+  });
+  struct Gone { int64_t lo, hi; int32_t series; };   // disjoint, ascending
+  std::vector<Gone> gone;
+  for (const int64_t k : hit) {
+    const int64_t lo = h_lohi[2 * k], hi = h_lohi[2 * k + 1];
+    if (lo < 0 || hi > NR) return fail(TSDB_E_HIP, "tsdbhip_remove: a range's rows lie outside the batch (internal)");
+    if (!gone.empty() && lo <= gone.back().hi && h_ranges[k].series == gone.back().series)
+      gone.back().hi = std::max(gone.back().hi, hi);
+    else
+      gone.push_back(Gone{lo, hi, h_ranges[k].series});
+  }
+  std::vector<int64_t> lost(N, 0);   // [resident position] rows the series loses
+  int64_t removed = 0;
+  uint64_t rm_q = 0, rm_v = 0;
+  for (const Gone& g : gone) {
+    lost[g.series] += g.hi - g.lo;
+    removed += g.hi - g.lo;
+    for (int64_t r = g.lo; r < g.hi; r++) {
+      rm_q += align16(c->h_qlen[r]);
+      rm_v += align16(c->h_vlen[r]);
+    }
+  }
+  int64_t emptied = 0, dropped = 0;
+  for (int64_t i = 0; i < N; i++) {
+    const int64_t had = c->h_srp[i + 1] - c->h_srp[i];
+    if (lost[i] && lost[i] == had) emptied++;
+    if (drop && lost[i] == had) dropped++;
+  }
+  const int64_t NR2 = NR - removed, N2 = N - dropped;
+  const uint64_t dead_q = c->qual_dead + rm_q, dead_v = c->val_dead + rm_v;
+  const bool do_pack = pack_wanted(c, pack_dead_pct, dead_q + dead_v);
+  // tsdbhip_load_cells' compaction errors: a row whose compaction failed is not resident, so an entry
+  // goes when a range covers its (series, base) whether or not the range covers a resident row;
+  // the others are renumbered with their series (new_of: null when no series is retired)
+  // One pass over the ranges: the entries are listed by series first (O(entries + ranges)).
+  auto settle_errs = [&](const std::vector<int64_t>* new_of) {
+    if (c->cmp_errs.empty() || (n_ranges == 0 && !new_of)) return;
+    const size_t E = c->cmp_errs.size();
+    std::unordered_map<int64_t, std::vector<size_t>> by_series;
+    for (size_t i = 0; i < E; i++) by_series[c->cmp_errs[i].series].push_back(i);
+    std::vector<uint8_t> went(E, 0);
+    for (int64_t k = 0; k < n_ranges; k++) {
+      const auto it = by_series.find(ranges[k].series_index);
+      if (it == by_series.end()) continue;
+      for (const size_t i : it->second)
+        if (ranges[k].from_s <= c->cmp_errs[i].base && c->cmp_errs[i].base < ranges[k].to_s) went[i] = 1;
+    }
+    std::vector<tsdbhip_ctx::CmpErr> kept;
+    for (size_t i = 0; i < E; i++) {
+      tsdbhip_ctx::CmpErr e = c->cmp_errs[i];
+      if (went[i] || e.series < 0 || e.series >= N) continue;
+      if (new_of) e.series = (*new_of)[e.series];
+      if (e.series >= 0) kept.push_back(e);
+    }
+    c->cmp_errs.swap(kept);
+  };
+  if (removed == 0 && dropped == 0 && !do_pack) {   // (nothing of the batch changes)
+    settle_errs(nullptr);
+    identity();
+    fill_info();
+    return 0;
+  }
+  // ---- the series after the call.  Retiring series leaves the others' relative order, in the
+  // batch and, their keys mapping monotonically, in the resident order ----
+  Mirrors m;
+  m.srp.assign(N2 + 1, 0);
+  std::vector<int64_t> new_of;         // old batch index -> new one (-1: retired)
+  std::vector<int32_t> new_pos(N);     // old resident position -> new one (-1: retired)
+  SeriesOrder order;
+  if (dropped) {
+    new_of.assign(N, -1);
+    std::vector<int32_t> old_of(N2);
+    const int64_t G_old = c->n_groups;
+    int32_t maxg = -1;
+    int64_t x = 0;
+    for (int64_t b = 0; b < N; b++) {
+      const int64_t p = pos[b];
+      if (lost[p] == c->h_srp[p + 1] - c->h_srp[p]) continue;
+      old_of[x] = (int32_t)b;
+      new_of[b] = x++;
+      if (c->h_group[p] < G_old) maxg = std::max(maxg, c->h_group[p]);
+    }
+    const int64_t G = (int64_t)maxg + 1;
+    auto key = [&](int64_t y) -> int64_t {   // y: new batch index
+      const int32_t g = c->h_group[pos[old_of[y]]];
+      return g < G_old ? g : g == G_old ? G : G + 1;
+    };
+    order = order_by_key(N2, G, key);
+    order.begin_fill(N2);
+    std::fill(new_pos.begin(), new_pos.end(), -1);
+    int64_t last = -1;
+    for (int64_t y = 0; y < N2; y++) {
+      const int64_t k = key(y), i = order.place(y, k), p = pos[old_of[y]];
+      new_pos[p] = (int32_t)i;
+      st_key[i] = (int32_t)k;
+    }
+    for (int64_t p = 0; p < N; p++) {   // (the row-level gather relies on it)
+      if (new_pos[p] < 0) continue;
+      if (new_pos[p] != last + 1) return fail(TSDB_E_HIP, "tsdbhip_remove: the resident order is not the keys' (internal)");
+      last = new_pos[p];
+    }
+  } else {
+    for (int64_t p = 0; p < N; p++) new_pos[p] = (int32_t)p;
+  }
+  for (int64_t p = 0; p < N; p++)
+    if (new_pos[p] >= 0) st_n_srp[new_pos[p] + 1] = c->h_srp[p + 1] - c->h_srp[p] - lost[p];
+  st_n_srp[0] = 0;
+  for (int64_t i = 0; i < N2; i++) st_n_srp[i + 1] += st_n_srp[i];
+  if (st_n_srp[N2] != NR2) return fail(TSDB_E_HIP, "tsdbhip_remove: row count mismatch (internal)");
+  std::copy(st_n_srp, st_n_srp + N2 + 1, m.srp.begin());
+  // the suspects: kept rows that carry ROW_UNSORTED and lie after their series' earliest removed
+  // row, as positions in the gathered array, and their series
+  std::vector<int64_t> sus;
+  std::vector<int32_t> sus_ser;
+  for (size_t a = 0; a < gone.size();) {
+    const int32_t p = gone[a].series;
+    size_t z = a;
+    int64_t out = m.srp[std::max<int32_t>(new_pos[p], 0)] + (gone[a].lo - c->h_srp[p]);   // the next kept row's new place
+    const size_t before = sus.size();
+    for (int64_t r = gone[a].lo; r < c->h_srp[p + 1]; r++) {
+      while (z < gone.size() && gone[z].series == p && gone[z].hi <= r) z++;
+      if (z < gone.size() && gone[z].series == p && gone[z].lo <= r) continue;   // (removed)
+      if (c->h_flags[r] & ROW_UNSORTED) sus.push_back(out);
+      out++;
+    }
+    if (sus.size() > before) sus_ser.push_back(new_pos[p]);
+    while (a < gone.size() && gone[a].series == p) a++;
+  }
+  const int64_t n_sus = (int64_t)sus.size(), n_ser = (int64_t)sus_ser.size();
+  // the pack's sizes: every kept row's aligned bytes, and whether one of them reads an int16 copy
+  BlobPack pack;
+  pack.on = do_pack;
+  bool need_v2_after = false;
+  if (do_pack) {
+    size_t z = 0;
+    for (int64_t r = 0; r < NR; r++) {
+      while (z < gone.size() && gone[z].hi <= r) z++;
+      if (z < gone.size() && gone[z].lo <= r) continue;
+      pack.live_q += align16(c->h_qlen[r]);
+      pack.live_v += align16(c->h_vlen[r]);
+      need_v2_after |= row_wants_val2(c->h_flags[r]);
+    }
+  }
+  // ---- allocations: nothing of the resident batch is released before the commit ----
+  if (const int rc = pack.ensure(c, fn, nomem_hint, NR2, need_v2_after)) return rc;
+  HIP_OK(c->rows2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RegRow)));
+  HIP_OK(c->srp2.ensure((size_t)(N2 + 1) * 8));
+  if (dropped) HIP_OK(c->gid2.ensure(std::max<size_t>(1, (size_t)N2) * 4));
+  HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
+  DevBuf idx_v2;   // (an int16 copy allocated only because the suspects' pass wants one goes with the call)
+  struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_idx_v2{idx_v2};
+  IndexPlan ip;
+  ip.fn = &fn;
+  ip.nomem_hint = nomem_hint;
+  ip.qp = c->qual.as<uint8_t>();
+  ip.vp = c->val.as<uint8_t>();
+  ip.v2p = c->val2.as<uint8_t>();   // (null when there is none)
+  ip.v2_buf = &idx_v2;
+  ip.qcap = c->qual.n;
+  ip.generic = opt_is(OPT_INDEX_GENERIC, 1);
+  if (n_sus) {
+    if (const int rc = reindex_ensure(c, n_sus)) return rc;
+    HIP_OK(c->tr_ser.ensure((size_t)n_ser * 4));
+    if (const int rc = ip.choose_route()) return rc;
+  }
+  // ---- queued work: the scans, the gather, the suspects' index and walk, the pack ----
+  HIP_OK(hipMemcpyAsync(c->srp2.p, st_n_srp, (size_t)(N2 + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (dropped && N2) HIP_OK(hipMemcpyAsync(c->gid2.p, st_key, (size_t)N2 * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(remove_scan(c->rm_diff.as<int32_t>(), c->rm_pos.as<int32_t>(), NR, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(tr.mark(2));
+  RemoveParams rp{};
+  rp.pos = c->rm_pos.as<int32_t>();
+  rp.srp_new = c->srp2.as<int64_t>();
+  rp.rows_old = c->rows.as<RowDesc>();
+  rp.reg_old = c->reg.as<RegRow>();
+  rp.n_series = N2;
+  rp.n_rows_old = NR;
+  rp.n_rows = NR2;
+  rp.rows_new = c->rows2.as<RowDesc>();
+  rp.reg_new = c->reg2.as<RegRow>();
+  HIP_OK(launch_remove_gather(rp, c->stream));
+  HIP_OK(tr.mark(3));
+  uint32_t idx_cnt[16] = {};
+  float t_index = 0;
+  if (n_sus) {
+    HIP_OK(hipMemcpyAsync(c->tr_ser.p, sus_ser.data(), (size_t)n_ser * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
+    if (const int rc = reindex_suspects(c, ip, sus.data(), n_sus, idx_cnt)) return rc;
+    HIP_OK(launch_trim_recede(rp.rows_new, rp.reg_new, rp.srp_new, c->tr_ser.as<int32_t>(), n_ser, ip.qp, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));   // (sus and sus_ser are pageable; the pass's time)
+    (void)hipEventElapsedTime(&t_index, c->ev[2], c->ev[3]);
+  }
+  HIP_OK(tr.mark(4));
+  if (const int rc = pack.queue(c, rp.rows_new, NR2)) return rc;
+  HIP_OK(tr.mark(5));
+  HIP_OK(m.download(c, NR2));
+  HIP_OK(tr.mark(6));
+  m.size_rows();
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (tr.on)
+    std::fprintf(stderr, "[trace remove] mark %.3f scans %.3f gather %.3f suspects %.3f pack %.3f desc_download %.3f ms\n",
+                 tr.ms(0, 1), tr.ms(1, 2), tr.ms(2, 3), tr.ms(3, 4), tr.ms(4, 5), tr.ms(5, 6));
+  m.split(c);
+  // ---- commit: from here on the context holds the remaining batch ----
+  m.commit(c, dropped ? &order : nullptr);
+  pack.settle(c, &ri, dead_q, dead_v);
+  settle_errs(dropped ? &new_of : nullptr);
+  std::memcpy(c->idx_cnt, idx_cnt, sizeof(c->idx_cnt));
+  c->idx_fused = n_sus ? ip.fused : false;
+  c->index_ms = t_index;
+  invalidate_derived(c);
+  const int rc = finish_classes(c);
+  if (dropped) {
+    for (int64_t b = 0; new_index && b < N; b++) new_index[b] = new_of[b];
+  } else {
+    identity();
+  }
+  ri.rows_removed = removed;
+  ri.series_emptied = emptied;
+  ri.series_dropped = dropped;
+  ri.rows_reindexed = n_sus;
   fill_info();
   return rc;
 }

@@ -627,6 +627,36 @@ hipError_t trim_pack_scan(const RowDesc* rows, int64_t n_rows, uint64_t* qdst, u
                           size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_trim_pack(const TrimPackParams& p, hipStream_t s);
 hipError_t launch_trim_offsets(RowDesc* rows, const uint64_t* qdst, const uint64_t* vdst, int64_t n_rows, hipStream_t s);
+// tsdbhip_remove (k_remove.hip): rows leave by (series, base-time range) from anywhere in a series.
+struct RemoveRange {          // one range as the device reads it (24 B)
+  int64_t from_s, to_s;       // the series' rows with from_s <= base < to_s go
+  int32_t series;             // the series' current resident position
+  int32_t pad;
+};
+struct RemoveMarkParams {
+  const RemoveRange* ranges;  // [n_ranges]
+  int64_t n_ranges;
+  const int64_t* srp_old;     // [n_series_old + 1]
+  const RowDesc* rows_old;    // [n_rows_old]
+  int64_t* lohi;              // [2 * n_ranges] (out) the rows [lo, hi) of rows_old the range covers
+  int32_t* diff;              // [n_rows_old + 1] zeroed by the caller; +1 at lo, -1 at hi
+};
+struct RemoveParams {
+  const int32_t* pos;         // [n_rows_old + 1] kept rows before old row r (remove_scan)
+  const int64_t* srp_new;     // [n_series + 1] series_row_ptr after the call (the caller's upload)
+  const RowDesc* rows_old;    // [n_rows_old]
+  const RegRow* reg_old;      // [n_rows_old]
+  int64_t n_series;           // series after the call
+  int64_t n_rows_old;
+  int64_t n_rows;             // rows after the call
+  RowDesc* rows_new;          // [n_rows] (out)
+  RegRow* reg_new;            // [n_rows] (out)
+};
+hipError_t launch_remove_mark(const RemoveMarkParams& p, hipStream_t s);
+// two scans: diff becomes the number of ranges covering each row (in place), pos the kept rows
+// before it, n_rows_old + 1 entries each
+hipError_t remove_scan(int32_t* diff, int32_t* pos, int64_t n_rows_old, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_remove_gather(const RemoveParams& p, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

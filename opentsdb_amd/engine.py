@@ -37,6 +37,7 @@ EXPORTS = [
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
     "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
+    "tsdbhip_remove",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
@@ -122,6 +123,7 @@ def lib():
         L.tsdbhip_append.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.AppendInfo)]
         L.tsdbhip_upsert.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.UpsertInfo)]
         L.tsdbhip_trim.argtypes =[vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
+        L.tsdbhip_remove.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_int32, vp, C.POINTER(abi.RemoveInfo)]
         L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
@@ -425,6 +427,27 @@ class Engine:
         info = abi.TrimInfo()
         _check(lib().tsdbhip_trim(self.ctx, int(cutoff_s), int(pack_dead_pct), C.byref(info)))
         return info
+
+    def remove(self, ranges, drop_empty: bool = False, pack_dead_pct: int = abi.TRIM_NO_PACK):
+        """tsdbhip_remove: the rows of `ranges` -- (series_index, from_s, to_s) triples, the index in
+        the batch numbering before the call -- leave the resident batch wherever they sit; with
+        drop_empty every series left without a row is retired and the batch renumbered.
+        pack_dead_pct as for trim.  Returns (abi.RemoveInfo, new_index): new_index[i] is series
+        i's batch index after the call, -1 for a retired one."""
+        ranges = list(ranges)
+        arr = (abi.RemoveRange * max(1, len(ranges)))()
+        for k, (i, a, b) in enumerate(ranges):
+            arr[k] = abi.RemoveRange(int(i), int(a), int(b))
+        n = C.c_int64(0)
+        # every loaded series, excluded ones included (a context the hook refuses is refused by the call itself)
+        if lib().tsdbhip_debug_loaded(self.ctx, C.byref(n), None) != 0:
+            n = C.c_int64(0)
+        new_index = np.full(n.value, -1, dtype=np.int64)
+        info = abi.RemoveInfo()
+        _check(lib().tsdbhip_remove(self.ctx, C.cast(arr, C.c_void_p) if ranges else None, len(ranges),
+                                    abi.REMOVE_DROP_EMPTY if drop_empty else 0, int(pack_dead_pct),
+                                    new_index.ctypes.data if len(new_index) else None, C.byref(info)))
+        return info, new_index
 
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""

@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .store import MockStore, make_batch
+from .store import MockStore, _tag_bytes, make_batch
 
 SECOND_MASK = 0xFFFFFFFF00000000
 
@@ -600,6 +600,11 @@ class ResidentSpans:
             ids[i] = g
         return ids, keys
 
+    @staticmethod
+    def _span_order(keys):
+        """Series keys of one metric in SpanCmp order, as MockStore.series lists them."""
+        return sorted(keys, key=lambda k: _tag_bytes(k[1]))
+
     def extend(self, scan_end_s: int, rescan_from_s: int | None = None):
         """Move the resident range's end to scan_end_s without a reload (Engine.append,
         tsdbhip_append): rescan [rescan_from_s, scan_end_s) -- by default from the largest
@@ -614,8 +619,9 @@ class ResidentSpans:
         delta = self.store.scan(self.metric, rescan_from_s, scan_end_s)
         old = dict(zip(self.span_keys, self.spans))
         dkeys = {sk for sk, _ in delta}
-        # SpanCmp order over the union of the keys: the store's own series order
-        merged_keys = [sk for sk in self.store.series(self.metric) if sk in old or sk in dkeys]
+        # SpanCmp order over the union of the keys: the store's own series order (a resident series
+        # whose rows have all left the store keeps its place)
+        merged_keys = self._span_order(set(old) | dkeys)
         index_of = {sk: i for i, sk in enumerate(merged_keys)}
         series_index = [index_of[sk] for sk, _ in delta]
         series_new = [sk not in old for sk, _ in delta]
@@ -631,7 +637,7 @@ class ResidentSpans:
         self.scan_end_s = scan_end_s
         return info
 
-    def refresh(self, from_s: int, to_s: int | None = None):
+    def refresh(self, from_s: int, to_s: int | None = None, remove_missing: bool = False):
         """Bring rows the store has changed inside the resident range up to date without a reload
         (Engine.upsert, tsdbhip_upsert): rescan [from_s, to_s) -- to_s defaults to the range's end
         -- and hand the engine that delta.  A rescanned row replaces the resident row of the same
@@ -639,7 +645,9 @@ class ResidentSpans:
         any other is inserted by base time (a back-filled gap); series the scan meets for the
         first time are inserted as extend inserts them.  The resident range does not move.  An
         upsert cannot remove rows: a resident row inside the window that the rescan no longer
-        returns needs a reload.  Returns the engine's abi.UpsertInfo."""
+        returns needs a reload -- or remove_missing=True, which first removes those rows as
+        single-row ranges (Engine.remove, tsdbhip_remove; their spans stay, row-less ones
+        included: retire_empty).  Returns the engine's abi.UpsertInfo."""
         if to_s is None:
             to_s = self.scan_end_s
         if from_s < self.scan_start_s or to_s > self.scan_end_s or to_s <= from_s:
@@ -647,15 +655,22 @@ class ResidentSpans:
                              f"[{self.scan_start_s}, {self.scan_end_s})")
         delta = self.store.scan(self.metric, from_s, to_s)
         drows = dict(delta)
-        for sk, rows in self.spans:
+        missing = []
+        for i, (sk, rows) in enumerate(self.spans):
             got = {r[0] for r in drows.get(sk, [])}
             for r in rows:
                 if from_s <= r[0] < to_s and r[0] not in got:
-                    raise ValueError(f"the resident row of base time {r[0]} is gone from the store: an upsert cannot "
-                                     "remove rows, reload the resident spans")
+                    if not remove_missing:
+                        raise ValueError(f"the resident row of base time {r[0]} is gone from the store: an upsert cannot "
+                                         "remove rows, reload the resident spans")
+                    missing.append((i, r[0], r[0] + 1))
+        if missing:
+            self.engine.remove(missing)
+            gone = {(i, b) for i, b, _ in missing}
+            self.spans = [(sk, [r for r in rows if (i, r[0]) not in gone]) for i, (sk, rows) in enumerate(self.spans)]
         old = dict(zip(self.span_keys, self.spans))
         # SpanCmp order over the union of the keys: the store's own series order (as extend)
-        merged_keys = [sk for sk in self.store.series(self.metric) if sk in old or sk in drows]
+        merged_keys = self._span_order(set(old) | set(drows))
         index_of = {sk: i for i, sk in enumerate(merged_keys)}
         series_index = [index_of[sk] for sk, _ in delta]
         series_new = [sk not in old for sk, _ in delta]
@@ -685,6 +700,44 @@ class ResidentSpans:
         self.spans = [(sk, [r for r in rows if r[0] >= scan_start_s]) for sk, rows in self.spans]
         self.scan_start_s = scan_start_s
         return info
+
+    def delete(self, query: TsdbQuery, drop_empty: bool = False, pack_dead_pct: int = 50):
+        """The delete query (TsdbQuery.setDelete(true)): `query` is answered as run answers it --
+        the reference returns the data it deletes --, then every row its scan returned leaves the
+        store (MockStore.delete_rows over the query's scan bounds and tag filter) and the
+        resident batch (Engine.remove, tsdbhip_remove: one range per matching resident series).
+        With drop_empty the spans left without rows are retired with their keys.  Returns
+        (DataPoints[], abi.RemoveInfo)."""
+        out = self.run(query)   # (run's range checks)
+        s, e = query.scan_bounds()
+        f = query._filters()
+        if f is None:   # an unknown tag name or literal value: no series matches
+            matching = []
+        else:
+            pred = f[0]
+            matching = [i for i, sk in enumerate(self.span_keys) if pred(sk[1])]
+            self.store.delete_rows(self.metric, s, e, pred)
+        info, new_index = self.engine.remove([(i, s, e) for i in matching], drop_empty, pack_dead_pct)
+        hit = set(matching)
+        self.spans = [(sk, [r for r in rows if not (i in hit and s <= r[0] < e)]) for i, (sk, rows) in enumerate(self.spans)]
+        if drop_empty:
+            self._retire(new_index)
+        return out, info
+
+    def retire_empty(self):
+        """Retire the spans without rows -- what trim, delete and refresh(remove_missing=True)
+        left behind -- from the resident batch (Engine.remove with drop_empty and no range) and
+        from spans / span_keys.  Returns the engine's abi.RemoveInfo."""
+        info, new_index = self.engine.remove([], True)
+        self._retire(new_index)
+        return info
+
+    def _retire(self, new_index):
+        kept = [(sk, rows) for sk, rows in self.spans if rows]
+        if [i for i, (_, rows) in enumerate(self.spans) if rows] != [i for i, x in enumerate(new_index) if x >= 0]:
+            raise RuntimeError("the engine retired other series than the row-less spans")
+        self.spans = kept
+        self.span_keys = [sk for sk, _ in kept]
 
     def run(self, query: TsdbQuery):
         """DataPoints[] of the query, keyed as TsdbQuery._run_raw keys them."""

@@ -202,6 +202,21 @@ class MockStore:
                 out.append((sk, rows))
         return out
 
+    def delete_rows(self, metric: str, scan_start_s: int, scan_end_s: int, tag_pred=None):
+        """A delete query's side of the scan (TsdbQuery.setDelete: SaltScanner.processRow issues
+        a DeleteRequest for every row key it scans): the rows scan() would return for the same
+        range and predicate leave the store.  Returns the deleted [(series_key, base_time), ...]."""
+        gone = []
+        for sk in self.series(metric):
+            if tag_pred is not None and not tag_pred(sk[1]):
+                continue
+            for base in sorted(b for (m, t, b) in self.rows if (m, t) == sk):
+                if scan_start_s <= base < scan_end_s:
+                    gone.append((sk, base))
+        for sk, base in gone:
+            del self.rows[(sk[0], sk[1], base)]
+        return gone
+
 
 def _tag_bytes(tags: tuple) -> bytes:
     return b"".join(k.to_bytes(3, "big") + v.to_bytes(3, "big") for k, v in tags)
