@@ -200,7 +200,8 @@ const char* tsdbhip_last_error(void);
  * PCT_VONLY, PCT_V6, SEL_FUSED, SEL_COLS, SEL_WIN, SEL_WAVE, SEL_REG, SELOPS, RAW_LERPW,
  * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT,
  * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit),
- * REGULAR (0: the regular tile lists through the ordinary streaming kernel, qualifiers read), TRACE, DBG
+ * REGULAR (0: the regular tile lists through the ordinary streaming kernel, qualifiers read),
+ * LAST_WALK (1: every tsdbhip_last answer through the walk kernel), TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
  * its production choice, which is every option's initial state.  The library reads no
  * environment variable: an inherited environment cannot change its kernels.  DBG is honoured
@@ -415,6 +416,50 @@ typedef struct {
 int tsdbhip_remove(tsdbhip_ctx* ctx, const tsdbhip_remove_range* ranges, int64_t n_ranges, uint32_t flags,
                    int32_t pack_dead_pct, int64_t* new_index /* N entries, may be NULL */,
                    tsdbhip_remove_info* info /* may be NULL */);
+/* The newest datapoint of each selected resident series: /api/query/last, that is
+ * QueryRpc.handleLastDataPointQuery (src/tsd/QueryRpc.java:346-494) -> TSUIDQuery.getLastPoint
+ * (src/meta/TSUIDQuery.java:161-217) -> Internal.GetLastDataPointCB (src/core/Internal.java:463-495).
+ * For a series with anchor time t (seconds) and back_scan >= 0 hours, h = t - t % 3600
+ * (Internal.baseTime): the rows with base h, h - 3600, ..., h - back_scan * 3600 are examined
+ * newest first and the first that exists is the answer row -- the series' latest row with
+ * max(0, h - back_scan * 3600) <= base <= h, since row bases are unique multiples of 3600 s.  A row
+ * newer than the anchor hour is never looked at; no such row: no answer (the reference's null).
+ * The datapoint is the last element of Internal.extractDataPoints' stable sort of the row by
+ * qualifier offset: the largest offset in ms, of equal offsets the one later in the cell -- the
+ * final datapoint of a well-formed row, also when it lies after t within the hour (the reference
+ * does not clip at "now").  ts_ms is Internal.getTimestampFromQualifier's, the value
+ * Cell.parseValue's: kind[i] 1 = an integer, bits[i] the Java long sign-extended from 1 / 2 / 4 / 8
+ * bytes; 2 = floating point, bits[i] the double's bits (a float32 widened); 0 = no answer, with
+ * ts_ms[i] = bits[i] = 0.  Every result is bit-exact.
+ * series_index are batch indices in the present numbering (tsdbhip_regroup's and tsdbhip_remove's),
+ * in any order, repeats allowed; NULL selects every resident series in batch order, and n_sel must
+ * then equal the number of loaded series.  Series the last tsdbhip_regroup excluded answer like any
+ * other: exclusion is a query's state, not the store's.  anchor_each, when given, holds each
+ * selected series' own anchor (the meta table's last-write time of its TSUID) and anchor_s is not
+ * used beyond its check; else every series is anchored at anchor_s ("now").  n_sel == 0 is a no-op.
+ * The call reads: it changes nothing of the batch, invalidates no cache, allocates scratch only,
+ * and leaves the cells of an earlier tsdbhip_rollup_run / tsdbhip_preagg_run alone.
+ * info: the selected series with and without an answer, and the answers by the route that found
+ * them (opentsdb_amd/csrc/k_last.hip; direct + copied + walked == found).
+ * Deviations, where no Java decides: an answer row that is a malformed cell (ROW_ERR) fails the
+ * whole call with TSDB_E_ILLEGAL_DATA (the reference throws only when the breakdown or the last
+ * cell is malformed); a malformed row that is no answer row is no error.  A resident row always
+ * holds a datapoint or is malformed, so the reference's NullPointerException on a row without
+ * data has no counterpart.
+ * TSDB_E_ILLEGAL_ARGUMENT: a null context, a null output pointer, n_sel < 0, a null selection
+ * with another n_sel, an index outside [0, N), back_scan < 0 (the reference's
+ * IllegalArgumentException), a negative anchor.  TSDB_E_NOT_IMPLEMENTED: a multi-device context, a
+ * rollup batch, a shard load, a context without a batch from tsdbhip_load / tsdbhip_load_cells /
+ * tsdbhip_synth.  Every check precedes any allocation. */
+typedef struct {
+  int64_t found, none;                 /* selected series with / without an answer */
+  int64_t direct, copied, walked;      /* answers by route, see k_last.hip; sum == found */
+  double  kernel_ms;                   /* hipEvent time of the call's kernels */
+} tsdbhip_last_info;
+int tsdbhip_last(tsdbhip_ctx* ctx, const int64_t* series_index, int64_t n_sel,
+                 int64_t anchor_s, const int64_t* anchor_each /* n_sel entries or NULL */,
+                 int32_t back_scan, int64_t* ts_ms, uint64_t* bits, uint8_t* kind,
+                 tsdbhip_last_info* info /* may be NULL */);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:

@@ -292,6 +292,21 @@ class RemoveInfo(C.Structure):
     ]
 
 
+class LastInfo(C.Structure):
+    """tsdbhip_last_info: the selected series with / without an answer, the answers by route."""
+    _fields_ = [
+        ("found", C.c_int64),
+        ("none", C.c_int64),
+        ("direct", C.c_int64),
+        ("copied", C.c_int64),
+        ("walked", C.c_int64),
+        ("kernel_ms", C.c_double),
+    ]
+
+
+LAST_NONE, LAST_INT, LAST_FLOAT = 0, 1, 2    # tsdbhip_last's kind[i]
+
+
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,
               ds_all: bool = False, rate: bool = False, counter: bool = False,

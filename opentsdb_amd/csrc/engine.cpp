@@ -427,6 +427,14 @@ struct tsdbhip_ctx {
   // (then the ranges covering each), the kept rows before each row
   DevBuf rm_ranges, rm_lohi, rm_diff, rm_pos;
   HostBuf rm_stage;                    // ... page-locked (the ranges, their rows, then series_row_ptr and the group keys)
+  // tsdbhip_last: the selected series' descriptor positions and anchors, the outputs, k_last_walk's
+  // list, the route counts with the error word; batch index -> descriptor position of every loaded
+  // series, on the host and on the device (a null selection reads it as it is), valid while
+  // last_pos_valid (invalidate_caches)
+  DevBuf ls_pos, ls_anchor, ls_ts, ls_bits, ls_kind, ls_list, ls_cnt, ls_pos_all;
+  HostBuf ls_stage;                    // ... page-locked (the counts and the error word read back)
+  std::vector<int32_t> h_pos;
+  bool last_pos_valid = false;
   std::vector<int64_t> h_srp;          // [n_series+1]
   std::vector<uint32_t> h_base;        // [n_rows]
   std::vector<uint32_t> h_ndp;         // [n_rows]
@@ -671,7 +679,7 @@ const char* const kOptNames[OPT_COUNT] = {
     "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "TRACE", "DBG"};
+    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "TRACE", "DBG"};
 int opt_index(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < OPT_COUNT; i++)
@@ -861,6 +869,7 @@ static void invalidate_caches(tsdbhip_ctx* c) {
   c->ro_meta_valid = false;
   c->lc_valid = false;
   c->calc_valid = false;
+  c->last_pos_valid = false;
   c->pg.cells = 0;   // (the pre-aggregate cells belong to the batch they came from)
   c->pg.qual_bytes = c->pg.value_bytes = 0;
 }
@@ -876,7 +885,8 @@ static void release_batch(tsdbhip_ctx* c) {
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
                     &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
-                    &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S, &c->rm_ranges, &c->rm_lohi, &c->rm_diff, &c->rm_pos})
+                    &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S, &c->rm_ranges, &c->rm_lohi, &c->rm_diff, &c->rm_pos,
+                    &c->ls_pos, &c->ls_anchor, &c->ls_ts, &c->ls_bits, &c->ls_kind, &c->ls_list, &c->ls_cnt, &c->ls_pos_all})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -952,6 +962,7 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   c->rg_rows.release();
   c->ap_stage.release();
   c->rm_stage.release();
+  c->ls_stage.release();
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
   for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
@@ -3937,6 +3948,112 @@ extern "C" int tsdbhip_remove(tsdbhip_ctx* c, const tsdbhip_remove_range* ranges
   ri.rows_reindexed = n_sus;
   fill_info();
   return rc;
+}
+
+// The newest datapoint of each selected series at or before its anchor hour:
+// TSUIDQuery.getLastPoint's walk back over at most back_scan hour rows as one search a series, and
+// the last element of Internal.extractDataPoints' sort of the row it finds.  A pure read: nothing
+// of the batch and no cache is touched, only scratch is allocated (the batch index -> position map
+// is a cache of its own, cleared with the others).  Everything is validated before anything is
+// allocated or queued.
+extern "C" int tsdbhip_last(tsdbhip_ctx* c, const int64_t* series_index, int64_t n_sel, int64_t anchor_s,
+                            const int64_t* anchor_each, int32_t back_scan, int64_t* ts_ms, uint64_t* bits, uint8_t* kind,
+                            tsdbhip_last_info* info) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  if (n_sel < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_sel below 0");
+  if (!ts_ms || !bits || !kind) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null output");
+  if (back_scan < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "back_scan below 0");   // (TSUIDQuery.getLastPoint's IllegalArgumentException)
+  if (anchor_s < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "anchor_s below 0");
+  MD_REFUSE(c, "tsdbhip_last");
+  CtxLock lk(c);
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_last over a rollup batch (tsdbhip_load_rollup)");
+  if (!c->regroup_ok)
+    return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_last needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                        "tsdbhip_synth (a shard holds a part of the series)");
+  const int64_t N = c->n_series_loaded;
+  if (N >= INT32_MAX) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_last over 2^31 - 1 series or more");
+  if (!series_index && n_sel != N)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "a null selection takes n_sel == " + std::to_string(N) + " (the loaded series), not " +
+                                             std::to_string(n_sel));
+  for (int64_t i = 0; series_index && i < n_sel; i++)
+    if (series_index[i] < 0 || series_index[i] >= N)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT,
+                  "series_index " + std::to_string(series_index[i]) + " outside [0, " + std::to_string(N) + ")");
+  for (int64_t i = 0; anchor_each && i < n_sel; i++)
+    if (anchor_each[i] < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "an anchor below 0");
+  tsdbhip_last_info li{};
+  if (n_sel == 0) {
+    if (info) *info = li;
+    return 0;
+  }
+  HIP_OK(hipSetDevice(c->device));
+  // batch index -> position in descriptor order (the visible series in resident order, then the excluded)
+  if (!c->last_pos_valid) {
+    c->h_pos.resize(N);
+    for (int64_t i = 0; i < N; i++) c->h_pos[c->h_orig[i]] = (int32_t)i;
+    HIP_OK(c->ls_pos_all.ensure((size_t)N * 4));
+    HIP_OK(h2d(c, c->ls_pos_all.p, c->h_pos.data(), (size_t)N * 4, c->stream));
+    c->last_pos_valid = true;
+  }
+  HIP_OK(c->ls_ts.ensure((size_t)n_sel * 8));
+  HIP_OK(c->ls_bits.ensure((size_t)n_sel * 8));
+  HIP_OK(c->ls_kind.ensure((size_t)n_sel));
+  HIP_OK(c->ls_list.ensure((size_t)n_sel * 16));
+  HIP_OK(c->ls_cnt.ensure(48));
+  HIP_OK(c->ls_stage.ensure(48));
+  LastParams p{};
+  p.rows = c->rows.as<RowDesc>();
+  p.reg = c->reg.as<RegRow>();
+  p.srp = c->srp.as<int64_t>();
+  p.qual = c->qual.as<uint8_t>();
+  p.val = c->val.as<uint8_t>();
+  p.val2 = c->val2.as<uint8_t>();   // (null when no resident row reads a copy)
+  p.pos = c->ls_pos_all.as<int32_t>();
+  std::vector<int32_t> sel;   // (outlives the queued upload)
+  if (series_index) {
+    HIP_OK(c->ls_pos.ensure((size_t)n_sel * 4));
+    sel.resize(n_sel);
+    for (int64_t i = 0; i < n_sel; i++) sel[i] = c->h_pos[series_index[i]];
+    HIP_OK(h2d(c, c->ls_pos.p, sel.data(), (size_t)n_sel * 4, c->stream));
+    p.pos = c->ls_pos.as<int32_t>();
+  }
+  if (anchor_each) {
+    HIP_OK(c->ls_anchor.ensure((size_t)n_sel * 8));
+    HIP_OK(h2d(c, c->ls_anchor.p, anchor_each, (size_t)n_sel * 8, c->stream));
+    p.anchor_each = c->ls_anchor.as<int64_t>();
+  }
+  p.anchor_s = anchor_s;
+  p.back_s = (int64_t)back_scan * 3600;
+  p.n_sel = n_sel;
+  p.walk_all = opt_is(OPT_LAST_WALK, 1) ? 1 : 0;
+  p.ts_ms = c->ls_ts.as<int64_t>();
+  p.bits = c->ls_bits.as<uint64_t>();
+  p.kind = c->ls_kind.as<uint8_t>();
+  p.list = c->ls_list.as<int64_t>();
+  p.cnt = c->ls_cnt.as<unsigned long long>();
+  p.err = reinterpret_cast<int32_t*>(c->ls_cnt.as<unsigned long long>() + 4);
+  HIP_OK(hipMemsetAsync(c->ls_cnt.p, 0, 48, c->stream));
+  HIP_OK(hipEventRecord(c->ev[0], c->stream));
+  HIP_OK(launch_last(p, c->stream));
+  HIP_OK(hipEventRecord(c->ev[1], c->stream));
+  HIP_OK(hipMemcpyAsync(c->ls_stage.p, c->ls_cnt.p, 48, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(ts_ms, p.ts_ms, (size_t)n_sel * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(bits, p.bits, (size_t)n_sel * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(kind, p.kind, (size_t)n_sel, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  const unsigned long long* const cnt = reinterpret_cast<const unsigned long long*>(c->ls_stage.p);
+  const int32_t derr = *reinterpret_cast<const int32_t*>(cnt + 4);
+  if (derr) return fail(derr, "tsdbhip_last: a series' answer row is a malformed cell (ROW_ERR)");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+  li.none = (int64_t)cnt[LC_NONE];
+  li.direct = (int64_t)cnt[LC_DIRECT];
+  li.copied = (int64_t)cnt[LC_COPIED];
+  li.walked = (int64_t)cnt[LC_WALKED];
+  li.found = li.direct + li.copied + li.walked;
+  li.kernel_ms = ms;
+  if (info) *info = li;
+  return 0;
 }
 
 extern "C" int tsdbhip_batch_sizes(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_rows, uint64_t* qual_bytes,

@@ -657,6 +657,30 @@ hipError_t launch_remove_mark(const RemoveMarkParams& p, hipStream_t s);
 // before it, n_rows_old + 1 entries each
 hipError_t remove_scan(int32_t* diff, int32_t* pos, int64_t n_rows_old, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_remove_gather(const RemoveParams& p, hipStream_t s);
+// tsdbhip_last (k_last.hip): the newest datapoint of each selected series at or before its anchor hour.
+enum : int { LC_NONE = 0, LC_DIRECT = 1, LC_COPIED = 2, LC_WALKED = 3 };   // LastParams.cnt slots
+struct LastParams {
+  const RowDesc* rows;
+  const RegRow* reg;
+  const int64_t* srp;          // series_row_ptr, every loaded series (descriptor order)
+  const uint8_t* qual;
+  const uint8_t* val;
+  const uint8_t* val2;         // the int16 copy; null: there is none (its rows walk)
+  const int32_t* pos;          // [n_sel] the selected series' positions in descriptor order
+  const int64_t* anchor_each;  // [n_sel] anchors (s), or null: anchor_s for every series
+  int64_t anchor_s;
+  int64_t back_s;              // back_scan hours in seconds
+  int64_t n_sel;
+  int32_t walk_all;            // option LAST_WALK: every answer through k_last_walk
+  int64_t* ts_ms;              // [n_sel] (out)
+  uint64_t* bits;              // [n_sel] (out)
+  uint8_t* kind;               // [n_sel] (out) 0 none, 1 integer, 2 floating point
+  int64_t* list;               // [2 * n_sel] k_last_walk's (output slot, row) pairs
+  unsigned long long* cnt;     // [4] zeroed by the caller: LC_* (LC_WALKED is the list's cursor)
+  int32_t* err;
+};
+// k_last_pick, then k_last_walk over the list it left (no synchronisation in between)
+hipError_t launch_last(const LastParams& p, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

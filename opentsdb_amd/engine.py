@@ -37,14 +37,14 @@ EXPORTS = [
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
     "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
-    "tsdbhip_remove",
+    "tsdbhip_remove", "tsdbhip_last",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
 OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "TRACE", "DBG"]
+           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "TRACE", "DBG"]
 
 IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
@@ -124,6 +124,7 @@ def lib():
         L.tsdbhip_upsert.argtypes = [vp, C.POINTER(abi.Batch), C.c_void_p, C.c_void_p, C.POINTER(abi.UpsertInfo)]
         L.tsdbhip_trim.argtypes =[vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
         L.tsdbhip_remove.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_int32, vp, C.POINTER(abi.RemoveInfo)]
+        L.tsdbhip_last.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(abi.LastInfo)]
         L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
@@ -448,6 +449,42 @@ class Engine:
                                     abi.REMOVE_DROP_EMPTY if drop_empty else 0, int(pack_dead_pct),
                                     new_index.ctypes.data if len(new_index) else None, C.byref(info)))
         return info, new_index
+
+    def last(self, series_index=None, anchor_s: int = 0, anchor_each=None, back_scan: int = 0):
+        """tsdbhip_last: the newest datapoint of each selected series at or before its anchor hour,
+        looking back over at most back_scan hour rows (/api/query/last).  series_index: batch indices
+        in the present numbering, any order, repeats allowed; None: every loaded series in batch
+        order.  anchor_each: one anchor (s) a selected series instead of anchor_s.  Returns
+        (ts_ms int64, bits uint64, kind uint8, abi.LastInfo): kind abi.LAST_INT -> bits is the long,
+        abi.LAST_FLOAT -> the double's bits, abi.LAST_NONE -> no answer (ts_ms = bits = 0)."""
+        if series_index is None:
+            n = C.c_int64(0)
+            # every loaded series, excluded ones included (a context the hook refuses is refused by the call itself)
+            if lib().tsdbhip_debug_loaded(self.ctx, C.byref(n), None) != 0:
+                n = C.c_int64(0)
+            sel, n_sel = None, n.value
+        else:
+            sel = np.ascontiguousarray(series_index, dtype=np.int64)
+            if sel.ndim != 1:
+                raise ValueError("series_index must be one-dimensional")
+            n_sel = len(sel)
+        each = None
+        if anchor_each is not None:
+            each = np.ascontiguousarray(anchor_each, dtype=np.int64)
+            if each.shape != (n_sel,):
+                raise ValueError("anchor_each needs one entry a selected series")
+        # (an empty array's data pointer may be null: the outputs are allocated with one entry at least)
+        ts = np.zeros(max(1, n_sel), np.int64)
+        bits = np.zeros(max(1, n_sel), np.uint64)
+        kind = np.zeros(max(1, n_sel), np.uint8)
+        info = abi.LastInfo()
+        t0 = time.perf_counter()
+        # (a null selection means every series: an empty one is handed over as some non-null pointer)
+        sel_p = None if sel is None else sel.ctypes.data if n_sel else ts.ctypes.data
+        _check(lib().tsdbhip_last(self.ctx, sel_p, n_sel, int(anchor_s), each.ctypes.data if each is not None and n_sel else None,
+                                  int(back_scan), ts.ctypes.data, bits.ctypes.data, kind.ctypes.data, C.byref(info)))
+        self.last_call_ms = (time.perf_counter() - t0) * 1e3
+        return ts[:n_sel], bits[:n_sel], kind[:n_sel], info
 
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""

@@ -561,6 +561,22 @@ class TsdbQuery:
             self.downsampler = saved
 
 
+class LastPoint:
+    """One answer of /api/query/last (IncomingDataPoint as Internal.GetLastDataPointCB fills it):
+    the timestamp in ms, the value -- a Python int for a Java long, a float for a double; Java's
+    toString rendering is the serializer's business -- and the series' TSUID as a hex string."""
+
+    __slots__ = ("timestamp", "value", "tsuid")
+
+    def __init__(self, timestamp: int, value, tsuid: str):
+        self.timestamp = timestamp
+        self.value = value
+        self.tsuid = tsuid
+
+    def __repr__(self):
+        return f"LastPoint({self.timestamp}, {self.value!r}, {self.tsuid!r})"
+
+
 class ResidentSpans:
     """Every span of one metric over [scan_start_s, scan_end_s), loaded once and kept in HBM;
     each query then only regroups the resident series (Engine.regroup, tsdbhip_regroup) instead
@@ -738,6 +754,60 @@ class ResidentSpans:
             raise RuntimeError("the engine retired other series than the row-less spans")
         self.spans = kept
         self.span_keys = [sk for sk, _ in kept]
+
+    @staticmethod
+    def tsuid_of(series_key) -> str:
+        """UniqueId.uidToString of a series key's TSUID: metric uid, then (tagk uid, tagv uid) pairs."""
+        m, tags = series_key
+        return (m.to_bytes(3, "big") + _tag_bytes(tags)).hex().upper()
+
+    def last(self, sub_queries, back_scan: int = 0, now_s: int | None = None, last_write_s=None):
+        """/api/query/last over the resident spans (QueryRpc.handleLastDataPointQuery): the newest
+        datapoint of every series the sub-queries name, by one Engine.last call (tsdbhip_last).
+        A sub-query is a mapping with "tsuids" (hex strings) or "metric" and exact "tags"; TSUIDs
+        win when both are given.  Every series is anchored at now_s (default: the clock) and looked
+        for over back_scan hour rows back from there -- or, with back_scan == 0 and last_write_s, a
+        map TSUID -> the meta table's last-write time in seconds, each at its own time, a series the
+        map does not hold having no answer (TSUIDQuery.getLastPoint's meta path).  Returns the
+        LastPoints in sub-query order with the nulls dropped, as FetchCB drops them; an unknown
+        TSUID, tag name or tag combination yields none.  A metric other than the resident one
+        raises ValueError, like run."""
+        if back_scan < 0:
+            raise ValueError("Backscan must be zero or a positive number")   # TSUIDQuery.getLastPoint
+        if now_s is None:
+            import time
+            now_s = int(time.time())
+        index_of = {self.tsuid_of(sk): i for i, sk in enumerate(self.span_keys)}
+        wanted = []   # TSUIDs in answer order; None: no such series
+        for sub in sub_queries:
+            if sub.get("tsuids"):
+                wanted += [t.upper() if t.upper() in index_of else None for t in sub["tsuids"]]
+                continue
+            if sub.get("metric") != self.metric:
+                raise ValueError("the sub-query is over another metric than the resident spans")
+            try:
+                tags = tuple(sorted((self.store.tagk.ids[k], self.store.tagv.ids[v]) for k, v in (sub.get("tags") or {}).items()))
+                t = self.tsuid_of((self.store.metrics.ids[self.metric], tags))
+            except KeyError:   # NoSuchUniqueName
+                t = None
+            wanted.append(t if t in index_of else None)
+        each = back_scan == 0 and last_write_s is not None
+        if each:
+            last_write_s = {k.upper(): v for k, v in last_write_s.items()}
+            wanted = [t if t in last_write_s else None for t in wanted]
+        asked = [t for t in wanted if t is not None]
+        if not asked:
+            return []
+        ts, bits, kind, _ = self.engine.last([index_of[t] for t in asked], anchor_s=now_s,
+                                             anchor_each=[int(last_write_s[t]) for t in asked] if each else None,
+                                             back_scan=back_scan)
+        out = []
+        for t, ms, b, k in zip(asked, ts, bits, kind):
+            if k == abi.LAST_INT:
+                out.append(LastPoint(int(ms), int(np.uint64(b).astype(np.int64)), t))
+            elif k == abi.LAST_FLOAT:
+                out.append(LastPoint(int(ms), float(np.uint64(b).view(np.float64)), t))
+        return out
 
     def run(self, query: TsdbQuery):
         """DataPoints[] of the query, keyed as TsdbQuery._run_raw keys them."""
