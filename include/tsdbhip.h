@@ -201,7 +201,8 @@ const char* tsdbhip_last_error(void);
  * RAW_SEL_TOP, RAW_SEL_REG, RO_FUSE, RO_RUNS, MULTI_FUSE, EMIT_HALF, HIST_WINDOW, HIST_WS, HIST_LAYOUT,
  * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit),
  * REGULAR (0: the regular tile lists through the ordinary streaming kernel, qualifiers read),
- * LAST_WALK (1: every tsdbhip_last answer through the walk kernel), TRACE, DBG
+ * LAST_WALK (1: every tsdbhip_last answer through the walk kernel),
+ * PUT_WALK (1: every resident row a tsdbhip_put rewrites through the walked route), TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
  * its production choice, which is every option's initial state.  The library reads no
  * environment variable: an inherited environment cannot change its kernels.  DBG is honoured
@@ -326,6 +327,76 @@ typedef struct {
 } tsdbhip_upsert_info;
 int tsdbhip_upsert(tsdbhip_ctx* ctx, const tsdbhip_batch* delta, const int64_t* series_index,
                    const uint8_t* series_new, tsdbhip_upsert_info* info /* may be NULL */);
+/* Datapoint writes merged into the resident batch, without a reload: what
+ * TSDB.addPoint -> addPointInternal -> storeIntoDB (src/core/TSDB.java:1012-1262) writes, as a later
+ * scan of the store would read it.  A put is a tsdbhip_upsert whose delta rows the device builds:
+ * no resident cell byte visits the host.
+ * `pts` is in write order.  Each point is encoded as the reference encodes it: a long in the
+ * smallest of 1 / 2 / 4 / 8 bytes with flags = length - 1, a float in 4 bytes under flags 0xB, a
+ * double in 8 bytes under flags 0xF; the qualifier is Internal.buildQualifier's, 4 bytes when
+ * timestamp & SECOND_MASK, else 2; the row base is storeIntoDB's.  Points of the call with identical
+ * (series, base, qualifier bytes) collapse to the last one (an HBase cell version; points_shadowed).
+ * For every touched (series, base) the new row is Compaction.compact
+ * (src/core/CompactionQueue.java:330-616) over the resident row's cell, as one column older than
+ * every put and read as ColumnDatapointIterator reads a column (single-datapoint fixups included),
+ * then the surviving puts as single-datapoint columns in write order: datapoints by ms offset; at a
+ * repeated offset the newest column's datapoint is kept and a discarded datapoint with other value
+ * bytes is an IllegalDataException unless TSDB_PUT_FIX_DUPLICATES is set; the meta byte only on a
+ * row of two or more datapoints, MS_MIXED_COMPACT when second and ms qualifiers mix; a row of one
+ * datapoint that needs no fixup stays as stored; a base with no resident row yields a new row from
+ * the puts alone.  series_index is a batch index in the present numbering (tsdbhip_regroup's,
+ * tsdbhip_remove's); the series must be resident (zero-row and excluded series are): a new series
+ * arrives through tsdbhip_upsert.
+ * Afterwards the context answers every entry point as a fresh tsdbhip_load of the resulting batch,
+ * followed by the tsdbhip_regroup that reproduces the present ids, would, bit for bit, with
+ * tsdbhip_upsert's exceptions (index debug and timing, dropped rollup / pre-aggregate cells, a
+ * renumbered compaction-error list, dead bytes where the rewritten rows sat and where a merged
+ * row's slot was larger than the row).  The merged cells go to the blobs' tail, 16-byte aligned, in
+ * slots sized from the resident lengths plus the puts' bytes.  A delta row takes one of three
+ * routes: rows_added (no resident row), rows_tail (a well-formed sorted resident row of one
+ * qualifier width and one value length, every put after its last offset: copied without decoding)
+ * and rows_walked (everything else; option PUT_WALK sends every rewritten row there; both give the
+ * same bytes).  rows_tail + rows_walked resident rows are rewritten.
+ * Every refusal leaves the batch as it was.  TSDB_E_ILLEGAL_ARGUMENT: a null context, null points
+ * with n > 0, n < 0 (or above 2^31 - 1), unknown flag bits, an index outside [0, N), kind outside
+ * 1..3, reserved != 0, timestamp < 0 or an ms timestamp above 9999999999999, a NaN or infinite
+ * float or double, a base at or above 2^32, a merged row beyond the "row too large" limit.
+ * TSDB_E_ILLEGAL_DATA (two deviations: the reference accepts the write and every later read of the
+ * row throws; the engine refuses the write so that the host can rescan and tsdbhip_upsert): a
+ * datapoint discarded at a repeated offset whose value bytes differ, without the fix flag -- the
+ * message names a conflicting (series, base, ms offset); a put whose qualifier already sits in the
+ * resident cell is a separate column here, whether HBase would have overwritten it depends on
+ * compaction write-back -- and a touched resident cell that is malformed; a touched (series, base)
+ * whose stored row failed its compaction at tsdbhip_load_cells counts as one (the row is not
+ * resident, the store still holds its cells and the compaction-error entry stays).
+ * TSDB_E_NOT_IMPLEMENTED: a
+ * multi-device context, a rollup batch, a shard load, and a touched resident cell whose offsets do
+ * not strictly increase inside the cell (found by the walk; ROW_UNSORTED alone may be owed to an
+ * earlier row).  TSDB_E_NOMEM as for tsdbhip_upsert.  n == 0 is a no-op.
+ * When several refusals apply, the one reported is the first of: an argument check, points in array
+ * order; then, over the touched rows in (resident position, base) order on the host, a duplicate
+ * among the call's own points or a row too large; a row on the compaction-error list; then what the
+ * device found -- a malformed cell before an unsorted one before a duplicate against a resident
+ * datapoint, each the smallest (touched row, ms offset).  The reference has no such order: it
+ * throws per row when the row is read. */
+enum { TSDB_PUT_LONG = 1, TSDB_PUT_FLOAT = 2, TSDB_PUT_DOUBLE = 3 };
+typedef struct {
+  int64_t series_index;   /* batch index, present numbering */
+  int64_t timestamp;      /* seconds or ms, exactly as TSDB.addPoint takes it */
+  uint64_t bits;          /* LONG: the Java long; FLOAT: float bits in the low 32; DOUBLE: the double's bits */
+  int32_t kind;           /* TSDB_PUT_* */
+  int32_t reserved;       /* 0 */
+} tsdbhip_point;
+#define TSDB_PUT_FIX_DUPLICATES 1u   /* tsd.storage.fix_duplicates */
+typedef struct {
+  int64_t points, points_shadowed;   /* given; dropped because a later point of the call has the same qualifier bytes */
+  int64_t rows_added, rows_tail, rows_walked;   /* delta rows by route; rows_tail + rows_walked = resident rows rewritten */
+  int64_t rows_reindexed;            /* as tsdbhip_upsert_info */
+  uint64_t qual_capacity, val_capacity, qual_dead, val_dead;
+  int32_t grew;
+  double kernel_ms;                  /* hipEvent time of the put kernel alone */
+} tsdbhip_put_info;
+int tsdbhip_put(tsdbhip_ctx* ctx, const tsdbhip_point* pts, int64_t n, uint32_t flags, tsdbhip_put_info* info /* may be NULL */);
 /* Old rows evicted from the resident batch and, on demand, the blobs re-laid without their dead
  * bytes.  Every resident row whose base time is < cutoff_s is evicted, of the
  * visible series and of those the last tsdbhip_regroup excluded; a series' rows are in base

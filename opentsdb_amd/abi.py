@@ -7,6 +7,7 @@ test-only oracle binding (oracle/oracle.py), which consumes the same boundary ty
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from collections.abc import Sequence
 
 import numpy as np
@@ -240,6 +241,62 @@ class UpsertInfo(C.Structure):
         ("qual_dead", C.c_uint64),
         ("val_dead", C.c_uint64),
         ("grew", C.c_int32),
+    ]
+
+
+PUT_LONG, PUT_FLOAT, PUT_DOUBLE = 1, 2, 3    # tsdbhip.h TSDB_PUT_*: tsdbhip_point.kind
+PUT_FIX_DUPLICATES = 1                       # tsdbhip.h TSDB_PUT_FIX_DUPLICATES (tsd.storage.fix_duplicates)
+
+
+class Point(C.Structure):
+    """tsdbhip_point: one datapoint write, as TSDB.addPoint takes it."""
+    _fields_ = [
+        ("series_index", C.c_int64),
+        ("timestamp", C.c_int64),
+        ("bits", C.c_uint64),
+        ("kind", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+POINT_DTYPE = np.dtype([("series_index", "<i8"), ("timestamp", "<i8"), ("bits", "<u8"), ("kind", "<i4"), ("reserved", "<i4")])
+
+
+def point_bits(kind: int, value) -> int:
+    """tsdbhip_point.bits of a value: the Java long, the float's bits in the low 32, the double's bits."""
+    if kind == PUT_LONG:
+        return int(value) & 0xFFFFFFFFFFFFFFFF
+    if kind == PUT_FLOAT:
+        return struct.unpack("<I", struct.pack("<f", value))[0]
+    if kind == PUT_DOUBLE:
+        return struct.unpack("<Q", struct.pack("<d", value))[0]
+    raise ValueError(f"kind {kind} is none of PUT_LONG, PUT_FLOAT, PUT_DOUBLE")
+
+
+def make_points(points) -> np.ndarray:
+    """[(series_index, timestamp, kind, value), ...] in write order -> a POINT_DTYPE array."""
+    points = list(points)
+    out = np.zeros(len(points), POINT_DTYPE)
+    for k, (i, ts, kind, value) in enumerate(points):
+        out[k] = (int(i), int(ts), point_bits(int(kind), value), int(kind), 0)
+    return out
+
+
+class PutInfo(C.Structure):
+    """tsdbhip_put_info: what a tsdbhip_put did to the resident batch."""
+    _fields_ = [
+        ("points", C.c_int64),
+        ("points_shadowed", C.c_int64),
+        ("rows_added", C.c_int64),
+        ("rows_tail", C.c_int64),
+        ("rows_walked", C.c_int64),
+        ("rows_reindexed", C.c_int64),
+        ("qual_capacity", C.c_uint64),
+        ("val_capacity", C.c_uint64),
+        ("qual_dead", C.c_uint64),
+        ("val_dead", C.c_uint64),
+        ("grew", C.c_int32),
+        ("kernel_ms", C.c_double),
     ]
 
 

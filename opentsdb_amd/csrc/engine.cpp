@@ -19,6 +19,7 @@
 #include <new>
 #include <thread>
 #include <numeric>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -433,6 +434,9 @@ struct tsdbhip_ctx {
   // last_pos_valid (invalidate_caches)
   DevBuf ls_pos, ls_anchor, ls_ts, ls_bits, ls_kind, ls_list, ls_cnt, ls_pos_all;
   HostBuf ls_stage;                    // ... page-locked (the counts and the error word read back)
+  // tsdbhip_put: the surviving puts, the delta rows, k_put's report
+  DevBuf pt_pts, pt_rows, pt_rep;
+  HostBuf pt_stage;                    // ... page-locked (the puts, then the rows, then the report read back)
   std::vector<int32_t> h_pos;
   bool last_pos_valid = false;
   std::vector<int64_t> h_srp;          // [n_series+1]
@@ -679,7 +683,7 @@ const char* const kOptNames[OPT_COUNT] = {
     "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "TRACE", "DBG"};
+    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TRACE", "DBG"};
 int opt_index(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < OPT_COUNT; i++)
@@ -886,7 +890,8 @@ static void release_batch(tsdbhip_ctx* c) {
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
                     &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
                     &c->tr_vdst, &c->up_dser, &c->up_lb, &c->up_hit, &c->up_S, &c->rm_ranges, &c->rm_lohi, &c->rm_diff, &c->rm_pos,
-                    &c->ls_pos, &c->ls_anchor, &c->ls_ts, &c->ls_bits, &c->ls_kind, &c->ls_list, &c->ls_cnt, &c->ls_pos_all})
+                    &c->ls_pos, &c->ls_anchor, &c->ls_ts, &c->ls_bits, &c->ls_kind, &c->ls_list, &c->ls_cnt, &c->ls_pos_all,
+                    &c->pt_pts, &c->pt_rows, &c->pt_rep})
     b->release();
   c->qual_dead = c->val_dead = 0;
   c->n_series_loaded = c->n_rows_loaded = 0;
@@ -963,6 +968,7 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   c->ap_stage.release();
   c->rm_stage.release();
   c->ls_stage.release();
+  c->pt_stage.release();
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
   for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
@@ -2935,14 +2941,27 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
 // Which rows replace one is found on the device (k_upsert_rank), the gather is k_upsert's merge of
 // two sorted lists, kept rows whose ROW_UNSORTED a replaced row may have caused are indexed again
 // (reindex_suspects), and k_recede's walk may flag any row of a touched series.
+//
+// tsdbhip_put is an upsert whose delta cells the device builds (DeviceDelta): the
+// batch it hands over carries the delta rows' bases and, as their lengths, the sizes of the slots
+// the cells are built in -- upper bounds -- and no cell byte.  Nothing is packed or uploaded; the
+// slots are zeroed, `build` runs once the slot descriptors are on the device and leaves each
+// row's exact qlen / vlen there, and everything after it is the upsert's.
 struct MergeInfo {
   int64_t series_added = 0, rows_added = 0, rows_replaced = 0, rows_reindexed = 0;
   bool grew = false;
 };
+struct DeviceDelta {
+  const char* fn;   // the entry point, for messages; its caller holds the context's lock
+  // queues the kernels that build the cells in the blobs qp / vp at drows' offsets, and waits for
+  // them; a refusal (non-zero) leaves the call with the resident batch as it was
+  std::function<int(uint8_t* qp, uint8_t* vp, RowDesc* drows)> build;
+};
 static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t* series_index, const uint8_t* series_new,
-                       const bool upsert, MergeInfo* mi) {
-  const std::string fn = upsert ? "tsdbhip_upsert" : "tsdbhip_append";
-  CtxLock lk(c);
+                       const bool upsert, MergeInfo* mi, const DeviceDelta* dev = nullptr) {
+  const std::string fn = dev ? dev->fn : upsert ? "tsdbhip_upsert" : "tsdbhip_append";
+  std::optional<CtxLock> lk;   // (a device-built delta's caller holds the lock)
+  if (!dev) lk.emplace(c);
   if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, fn + " over a rollup batch (tsdbhip_load_rollup)");
   const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
   if (!c->regroup_ok)
@@ -3061,9 +3080,13 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   }
   // (not zero-filled first and not single-threaded: for a large delta this pass is the call's cost)
   const size_t hq_n = qtot - q0, hv_n = vtot - v0;
-  std::unique_ptr<uint8_t[]> hq(new (std::nothrow) uint8_t[hq_n + 1]), hv(new (std::nothrow) uint8_t[hv_n + 1]);
-  if (!hq || !hv) return fail(TSDB_E_NOMEM, fn + ": no host memory to stage the delta's cells");
-  pack_cells(hq.get(), hv.get(), b, drow.data(), rd.data(), DR, q0, v0);
+  std::unique_ptr<uint8_t[]> hq, hv;
+  if (!dev) {
+    hq.reset(new (std::nothrow) uint8_t[hq_n + 1]);
+    hv.reset(new (std::nothrow) uint8_t[hv_n + 1]);
+    if (!hq || !hv) return fail(TSDB_E_NOMEM, fn + ": no host memory to stage the delta's cells");
+    pack_cells(hq.get(), hv.get(), b, drow.data(), rd.data(), DR, q0, v0);
+  }
   HIP_OK(hipSetDevice(c->device));
   // ---- allocations: nothing of the resident batch is released before the commit ----
   BlobHold hold;
@@ -3127,8 +3150,8 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     HIP_OK(hipMemsetAsync(vp + c->val_bytes, 0, hold.v.n - c->val_bytes, c->stream));
   }
   HIP_OK(tr.mark(1));
-  if (hq_n) HIP_OK(h2d(c, qp + q0, hq.get(), hq_n, c->stream));
-  if (hv_n) HIP_OK(h2d(c, vp + v0, hv.get(), hv_n, c->stream));
+  if (hq_n) HIP_OK(dev ? hipMemsetAsync(qp + q0, 0, hq_n, c->stream) : h2d(c, qp + q0, hq.get(), hq_n, c->stream));
+  if (hv_n) HIP_OK(dev ? hipMemsetAsync(vp + v0, 0, hv_n, c->stream) : h2d(c, vp + v0, hv.get(), hv_n, c->stream));
   if (!grow_q) HIP_OK(hipMemsetAsync(qp + qtot, 0, BLOB_SLACK, c->stream));   // (the slack past the new end reads as zeros)
   if (!grow_v) HIP_OK(hipMemsetAsync(vp + vtot, 0, BLOB_SLACK, c->stream));
   if (DR) HIP_OK(hipMemcpyAsync(c->ap_rows.p, rd.data(), (size_t)DR * sizeof(RowDesc), hipMemcpyHostToDevice, c->stream));
@@ -3159,6 +3182,15 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     HIP_OK(hipMemcpyAsync(c->ap_touch.p, touched, (size_t)n_touched * 4, hipMemcpyHostToDevice, c->stream));
   if (upsert && DR) HIP_OK(hipMemcpyAsync(c->up_dser.p, dser.data(), (size_t)DR * 4, hipMemcpyHostToDevice, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));   // (rd, hq, hv, dser are pageable: staged before they leave scope)
+  if (dev) {
+    if (const int rc = dev->build(qp, vp, c->ap_rows.as<RowDesc>())) {
+      // a refusal: the slots in blobs that stay resident read as zeros again, as the slack did
+      if (!grow_q && hq_n) (void)hipMemsetAsync(qp + q0, 0, hq_n, c->stream);
+      if (!grow_v && hv_n) (void)hipMemsetAsync(vp + v0, 0, hv_n, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      return rc;
+    }
+  }
   // index only the delta: its descriptors in their own array, the blob base pointers as they are
   HIP_OK(hipMemsetAsync(c->err.p, 0, 4, c->stream));
   const IndexBufs ib{c->hint.as<uint8_t>(), c->ilist.as<int32_t>(), c->icnt.as<uint32_t>()};
@@ -3204,6 +3236,11 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     (void)hipEventElapsedTime(&t_index, ev[2], ev[3]);
     for (const RowDesc& d : rd)
       if (row_wants_val2(d.flags)) { need_val2 = true; break; }
+    for (int64_t k = 0; dev && k < DR; k++) {   // what a slot held beyond its cell is dead from the start
+      const int64_t r = drow[k];
+      dead_q += align16(b->row_qual_off[r + 1] - b->row_qual_off[r]) - align16(rd[k].qlen);
+      dead_v += align16(b->row_val_off[r + 1] - b->row_val_off[r]) - align16(rd[k].vlen);
+    }
     if (need_val2 && generic) {   // test hook: the sequential path writes the copy in a second pass
       if (const int rc = ip.need_v2()) return rc;
       HIP_OK(hipEventRecord(ev[2], c->stream));
@@ -3307,6 +3344,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
       std::fprintf(stderr, "[trace append] grow_copy %.3f upload %.3f index %.3f scan_gather %.3f desc_download %.3f ms\n",
                    t[0], t[1], t[2], t[3], t[4]);
     } else {   // (rank_download: the ranks' way to the host and the host's pass over them)
+      std::fprintf(stderr, dev ? "[trace put] (upload: the slots zeroed and k_put) " : "");
       std::fprintf(stderr, "[trace upsert] grow_copy %.3f upload %.3f index_rank %.3f (delta_index %.3f) hit_scan %.3f rank_download %.3f "
                            "scan_gather %.3f suspects %.3f (suspect_index %.3f) recede %.3f desc_download %.3f ms\n",
                    t[0], t[1], tr.ms(2, 6), t_index, tr.ms(6, 7), tr.ms(7, 8), tr.ms(8, 9), tr.ms(9, 10), t_sus, tr.ms(10, 4), t[4]);
@@ -3391,6 +3429,265 @@ extern "C" int tsdbhip_upsert(tsdbhip_ctx* c, const tsdbhip_batch* delta, const 
   if (rc || !info) return rc;
   fill_edit_info(info, mi, c);
   info->rows_reindexed = mi.rows_reindexed;
+  return 0;
+}
+
+// Datapoint writes merged into the resident batch.  The host validates the points,
+// buckets them by (series position, base) -- a binary search in h_base a delta row -- drops the
+// points a later one of the call shadows (same qualifier bytes) or beats (same offset: the newest
+// column's datapoint is the one Compaction keeps, and a loser with other value bytes is the
+// duplicate it throws on), and sizes each delta row's slot from the mirrors.  Its work is
+// O(points log points); no resident cell byte is read here.  k_put builds the cells; merge_delta
+// does the rest as for an upsert.
+namespace {
+struct PutKey {
+  int32_t pos;       // resident position of the series
+  uint32_t base;
+  uint32_t off_ms;
+  int32_t order;     // the point's place in the call
+  uint32_t meta;     // PutPoint.meta
+  uint64_t bits;     // the value's bytes in the low `length` bytes
+};
+}  // namespace
+
+extern "C" int tsdbhip_put(tsdbhip_ctx* c, const tsdbhip_point* pts, int64_t n, uint32_t flags, tsdbhip_put_info* info) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_put");
+  if (n < 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "n < 0");
+  if (n > 0 && !pts) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  if (flags & ~TSDB_PUT_FIX_DUPLICATES) return fail(TSDB_E_ILLEGAL_ARGUMENT, "unknown flag bits");
+  if (n > INT32_MAX) return fail(TSDB_E_ILLEGAL_ARGUMENT, "more than 2^31 - 1 points");
+  const std::string fn = "tsdbhip_put";
+  CtxLock lk(c);
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, fn + " over a rollup batch (tsdbhip_load_rollup)");
+  if (!c->regroup_ok)
+    return fail(TSDB_E_NOT_IMPLEMENTED, fn + " needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
+                                             "tsdbhip_synth (a shard's groups are numbered globally)");
+  const int64_t N = c->n_series_loaded;
+  tsdbhip_put_info out{};
+  out.points = n;
+  if (n == 0) {
+    fill_blob_info(&out, c);
+    if (info) *info = out;
+    return 0;
+  }
+  std::vector<int32_t> pos(std::max<int64_t>(N, 1));   // batch index -> resident position
+  for (int64_t i = 0; i < N; i++) pos[c->h_orig[i]] = (int32_t)i;
+  // ---- validation and encoding lengths (TSDB.addPointInternal, checkTimestampAndTags) ----
+  constexpr uint64_t SECOND_MASK = 0xFFFFFFFF00000000ull;
+  std::vector<PutKey> key(n);
+  for (int64_t i = 0; i < n; i++) {
+    const tsdbhip_point& t = pts[i];
+    const std::string at = "point " + std::to_string(i) + ": ";
+    if (t.series_index < 0 || t.series_index >= N)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "series_index " + std::to_string(t.series_index) + " outside [0, " + std::to_string(N) + ")");
+    if (t.kind < TSDB_PUT_LONG || t.kind > TSDB_PUT_DOUBLE) return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "kind outside 1..3");
+    if (t.reserved != 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "reserved != 0");
+    const bool ms = ((uint64_t)t.timestamp & SECOND_MASK) != 0;
+    if (t.timestamp < 0 || (ms && t.timestamp > 9999999999999LL))
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "invalid timestamp " + std::to_string(t.timestamp));
+    const int64_t sec = ms ? t.timestamp / 1000 : t.timestamp;
+    const int64_t base = sec - sec % 3600;
+    if (base > 0xFFFFFFFFLL) return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "row base time at or above 2^32");
+    PutKey& k = key[i];
+    k.pos = pos[t.series_index];
+    k.base = (uint32_t)base;
+    k.off_ms = (uint32_t)(ms ? t.timestamp - base * 1000 : (t.timestamp - base) * 1000);
+    k.order = (int32_t)i;
+    uint32_t len, fl;
+    if (t.kind == TSDB_PUT_LONG) {
+      const int64_t v = (int64_t)t.bits;
+      len = v >= INT8_MIN && v <= INT8_MAX ? 1 : v >= INT16_MIN && v <= INT16_MAX ? 2 : v >= INT32_MIN && v <= INT32_MAX ? 4 : 8;
+      fl = len - 1;
+    } else if (t.kind == TSDB_PUT_FLOAT) {
+      if ((t.bits & 0x7F800000ull) == 0x7F800000ull) return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "value is NaN or Infinite");
+      len = 4;
+      fl = 0xB;
+    } else {
+      if ((t.bits & 0x7FF0000000000000ull) == 0x7FF0000000000000ull)
+        return fail(TSDB_E_ILLEGAL_ARGUMENT, at + "value is NaN or Infinite");
+      len = 8;
+      fl = 0xF;
+    }
+    k.bits = len == 8 ? t.bits : t.bits & ((1ull << (8 * len)) - 1);
+    k.meta = len | fl << 8 | (ms ? 4u : 2u) << 16;
+  }
+  // ---- buckets: by (series position, base, offset), the newest first at an offset ----
+  std::sort(key.begin(), key.end(), [](const PutKey& x, const PutKey& y) {
+    if (x.pos != y.pos) return x.pos < y.pos;
+    if (x.base != y.base) return x.base < y.base;
+    if (x.off_ms != y.off_ms) return x.off_ms < y.off_ms;
+    return x.order > y.order;
+  });
+  const bool fix = (flags & TSDB_PUT_FIX_DUPLICATES) != 0;
+  std::vector<PutPoint> pp;
+  std::vector<PutRow> pr;
+  std::vector<int64_t> d_srp(1, 0), d_index;    // the delta as a batch: its series ...
+  std::vector<int32_t> row_pos;                 // each delta row's series position
+  std::vector<uint32_t> d_base;                 // ... its rows' bases and, as the cells' lengths, their slots' sizes
+  std::vector<uint64_t> d_qoff(1, 0), d_voff(1, 0);
+  pp.reserve(n);
+  int64_t rows_added = 0;
+  for (int64_t i = 0; i < n;) {
+    const PutKey& h = key[i];
+    if (d_index.empty() || d_index.back() != c->h_orig[h.pos]) {
+      if (!d_index.empty()) d_srp.push_back((int64_t)pr.size());
+      d_index.push_back(c->h_orig[h.pos]);
+    }
+    PutRow R{};
+    R.p0 = (int32_t)pp.size();
+    int64_t j = i;
+    for (; j < n && key[j].pos == h.pos && key[j].base == h.base;) {
+      // one offset: the newest point is kept; an older one with its qualifier bytes is shadowed, any
+      // other older one is the datapoint Compaction discards, compared with the kept value's bytes
+      const PutKey& w = key[j];
+      uint32_t seen = 0;   // qualifier bytes met at this offset: bit (flag nibble | ms << 4)
+      int64_t e = j;
+      for (; e < n && key[e].pos == w.pos && key[e].base == w.base && key[e].off_ms == w.off_ms; e++) {
+        const PutKey& o = key[e];
+        const uint32_t qbit = 1u << (((o.meta >> 8) & 0xF) | ((o.meta >> 16) == 4 ? 16u : 0u));
+        if (seen & qbit) { out.points_shadowed++; continue; }
+        seen |= qbit;
+        if (e != j && !fix && ((o.meta & 0xFF) != (w.meta & 0xFF) || o.bits != w.bits))
+          return fail(TSDB_E_ILLEGAL_DATA,
+                      fn + ": Duplicate timestamp for series " + std::to_string(c->h_orig[w.pos]) + ", base " +
+                          std::to_string(w.base) + ", ms_offset=" + std::to_string(w.off_ms) +
+                          " among the call's points; set TSDB_PUT_FIX_DUPLICATES (tsd.storage.fix_duplicates)");
+      }
+      PutPoint t{};
+      t.bits = w.bits;
+      t.off_ms = w.off_ms;
+      t.meta = w.meta;
+      t.qpre = R.qsum;
+      t.vpre = R.vsum;
+      if ((uint64_t)R.qsum + 4 > 0xFFFFFFFFull || (uint64_t)R.vsum + 9 > 0xFFFFFFFFull) return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
+      R.qsum += w.meta >> 16;
+      R.vsum += w.meta & 0xFF;
+      R.widths |= (w.meta >> 16) == 4 ? 2u : 1u;
+      pp.push_back(t);
+      j = e;
+    }
+    R.np = (int32_t)pp.size() - R.p0;
+    // the resident row of this base, by binary search in the series' mirror
+    const int64_t r0 = c->h_srp[h.pos], r1 = c->h_srp[h.pos + 1];
+    const auto it = std::lower_bound(c->h_base.begin() + r0, c->h_base.begin() + r1, h.base);
+    const int64_t r = it - c->h_base.begin();
+    R.res = r < r1 && *it == h.base ? r : -1;
+    const uint64_t sq = (uint64_t)R.qsum + (R.res >= 0 ? c->h_qlen[r] : 0);
+    const uint64_t sv = (uint64_t)R.vsum + 1 + (R.res >= 0 ? c->h_vlen[r] : 0);
+    if (sq > 0xFFFFFFFFull || sv > 0xFFFFFFFFull) return fail(TSDB_E_ILLEGAL_ARGUMENT, "row too large");
+    if (R.res < 0) rows_added++;
+    d_base.push_back(h.base);
+    row_pos.push_back(h.pos);
+    d_qoff.push_back(d_qoff.back() + sq);
+    d_voff.push_back(d_voff.back() + sv);
+    pr.push_back(R);
+    i = j;
+  }
+  d_srp.push_back((int64_t)pr.size());
+  const int64_t D = (int64_t)d_index.size(), DR = (int64_t)pr.size();
+  // A row that failed query-time compaction at tsdbhip_load_cells is not resident: only its entry in
+  // the compaction-error list makes a read of that hour throw, as the reference's does.  The store
+  // still holds the bad cells, so a row built from the puts alone would answer what the reference
+  // refuses: such a row is a malformed touched cell.
+  if (!c->cmp_errs.empty()) {
+    std::vector<std::pair<int64_t, int64_t>> bad;
+    for (const auto& e : c->cmp_errs) bad.emplace_back(e.series, e.base);
+    std::sort(bad.begin(), bad.end());
+    for (int64_t k = 0; k < DR; k++) {
+      const int64_t x = c->h_orig[row_pos[k]];
+      if (std::binary_search(bad.begin(), bad.end(), std::make_pair(x, (int64_t)d_base[k])))
+        return fail(TSDB_E_ILLEGAL_DATA, fn + ": the stored row of series " + std::to_string(x) + ", base " + std::to_string(d_base[k]) +
+                                             " failed its compaction at tsdbhip_load_cells; rescan the row and tsdbhip_upsert it");
+    }
+  }
+  static const uint8_t no_cells = 0;   // (the delta's cells are built on the device: nothing reads these)
+  std::vector<int32_t> d_gid(D, 0);
+  std::vector<uint8_t> d_new(D, 0);
+  tsdbhip_batch db{};
+  db.n_series = D;
+  db.n_rows = DR;
+  db.series_row_ptr = d_srp.data();
+  db.row_base_time = d_base.data();
+  db.row_qual_off = d_qoff.data();
+  db.row_val_off = d_voff.data();
+  db.qual = &no_cells;
+  db.val = &no_cells;
+  db.group_id = d_gid.data();
+  HIP_OK(hipSetDevice(c->device));
+  const size_t pts_bytes = pp.size() * sizeof(PutPoint), rows_bytes = (size_t)DR * sizeof(PutRow), rep_bytes = PR_SLOTS * 8;
+  HIP_OK(c->pt_pts.ensure(pts_bytes));
+  HIP_OK(c->pt_rows.ensure(rows_bytes));
+  HIP_OK(c->pt_rep.ensure(rep_bytes));
+  HIP_OK(c->pt_stage.ensure(pts_bytes + rows_bytes + 2 * rep_bytes));
+  uint8_t* const st = reinterpret_cast<uint8_t*>(c->pt_stage.p);
+  std::memcpy(st, pp.data(), pts_bytes);
+  std::memcpy(st + pts_bytes, pr.data(), rows_bytes);
+  unsigned long long* const rep0 = reinterpret_cast<unsigned long long*>(st + pts_bytes + rows_bytes);
+  unsigned long long* const rep = rep0 + PR_SLOTS;
+  for (int k = 0; k < PR_SLOTS; k++) rep0[k] = k < PR_MALFORMED ? 0ull : ~0ull;
+  float kernel_ms = 0;
+  double build_ms = 0;
+  const double prep_ms = ms_since(t_begin);
+  DeviceDelta dev;
+  dev.fn = "tsdbhip_put";
+  dev.build = [&](uint8_t* qp, uint8_t* vp, RowDesc* drows) -> int {
+    const auto t_build = std::chrono::steady_clock::now();
+    HIP_OK(hipMemcpyAsync(c->pt_pts.p, st, pts_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->pt_rows.p, st + pts_bytes, rows_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->pt_rep.p, rep0, rep_bytes, hipMemcpyHostToDevice, c->stream));
+    PutParams p{};
+    p.rows = c->rows.as<RowDesc>();
+    p.reg = c->reg.as<RegRow>();
+    p.qual = qp;
+    p.val = vp;
+    p.pts = c->pt_pts.as<PutPoint>();
+    p.prow = c->pt_rows.as<PutRow>();
+    p.drows = drows;
+    p.n_rows = DR;
+    p.walk_all = opt_is(OPT_PUT_WALK, 1) ? 1 : 0;
+    p.fix = fix ? 1 : 0;
+    p.rep = c->pt_rep.as<unsigned long long>();
+    HIP_OK(hipEventRecord(c->ev[0], c->stream));
+    HIP_OK(launch_put(p, c->stream));
+    HIP_OK(hipEventRecord(c->ev[1], c->stream));
+    HIP_OK(hipMemcpyAsync(rep, c->pt_rep.p, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&kernel_ms, c->ev[0], c->ev[1]);
+    build_ms = ms_since(t_build);
+    auto where = [&](unsigned long long w) {
+      return "series " + std::to_string(c->h_orig[row_pos[(size_t)(w >> 32)]]) + ", base " + std::to_string(d_base[(size_t)(w >> 32)]);
+    };
+    if (rep[PR_MALFORMED] != ~0ull)
+      return fail(TSDB_E_ILLEGAL_DATA, fn + ": the resident cell of " + where(rep[PR_MALFORMED]) + " is malformed; rescan the row and tsdbhip_upsert it");
+    if (rep[PR_UNSORTED] != ~0ull)
+      return fail(TSDB_E_NOT_IMPLEMENTED, fn + ": the offsets inside the resident cell of " + where(rep[PR_UNSORTED]) +
+                                              " do not strictly increase (at ms_offset=" + std::to_string((uint32_t)rep[PR_UNSORTED]) + ")");
+    if (rep[PR_CONFLICT] != ~0ull)
+      return fail(TSDB_E_ILLEGAL_DATA, fn + ": Duplicate timestamp for " + where(rep[PR_CONFLICT]) + ", ms_offset=" +
+                                           std::to_string((uint32_t)rep[PR_CONFLICT]) +
+                                           ": the resident datapoint has other value bytes; set TSDB_PUT_FIX_DUPLICATES "
+                                           "(tsd.storage.fix_duplicates), or rescan the row and tsdbhip_upsert it");
+    return 0;
+  };
+  MergeInfo mi;
+  const int rc = merge_delta(c, &db, d_index.data(), d_new.data(), true, &mi, &dev);
+  if (rc) return rc;
+  if (opt_is(OPT_TRACE, 1))
+    std::fprintf(stderr, "[trace put] points %lld rows %lld k_put %.3f host_prep %.3f build %.3f call %.3f ms\n", (long long)pp.size(),
+                 (long long)DR, kernel_ms, prep_ms, build_ms, ms_since(t_begin));
+  out.rows_added = rows_added;
+  out.rows_tail = (int64_t)rep[PR_TAIL];
+  out.rows_walked = (int64_t)rep[PR_WALKED];
+  out.rows_reindexed = mi.rows_reindexed;
+  fill_blob_info(&out, c);
+  out.grew = mi.grew ? 1 : 0;
+  out.kernel_ms = kernel_ms;
+  if (info) *info = out;
   return 0;
 }
 

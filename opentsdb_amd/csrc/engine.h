@@ -681,6 +681,39 @@ struct LastParams {
 };
 // k_last_pick, then k_last_walk over the list it left (no synchronisation in between)
 hipError_t launch_last(const LastParams& p, hipStream_t s);
+// tsdbhip_put (k_put.hip): the merged cells of the touched rows, built at the blobs' tail.
+struct PutPoint {    // a surviving put; a delta row's are consecutive, by strictly increasing offset
+  uint64_t bits;     // the value's big-endian bytes in the low `length` bytes
+  uint32_t off_ms;   // offset from the row base, ms
+  uint32_t meta;     // value length | qualifier flag nibble << 8 | qualifier width << 16
+  uint32_t qpre;     // qualifier bytes of the row's puts before this one
+  uint32_t vpre;     // value bytes of them
+};
+static_assert(sizeof(PutPoint) == 24, "PutPoint layout");
+struct PutRow {      // a delta row
+  int64_t res;       // the resident row of its (series, base), or -1
+  int32_t p0, np;    // its puts in PutParams.pts
+  uint32_t qsum, vsum;   // their qualifier and value bytes
+  uint32_t widths;   // bit 0: a put with a 2-byte qualifier, bit 1: one with a 4-byte qualifier
+  uint32_t pad;
+};
+static_assert(sizeof(PutRow) == 32, "PutRow layout");
+// PutParams.rep slots: the route counts, then the smallest (delta row << 32 | ms offset) of each refusal
+enum : int { PR_TAIL = 0, PR_WALKED = 1, PR_MALFORMED = 2, PR_UNSORTED = 3, PR_CONFLICT = 4, PR_SLOTS = 5 };
+struct PutParams {
+  const RowDesc* rows;         // the resident descriptors
+  const RegRow* reg;
+  uint8_t* qual;               // the blobs: resident cells read, the delta's slots written
+  uint8_t* val;
+  const PutPoint* pts;
+  const PutRow* prow;          // [n_rows]
+  RowDesc* drows;              // [n_rows] the delta's descriptors: qoff / voff / base given, qlen / vlen written
+  int64_t n_rows;
+  int32_t walk_all;            // option PUT_WALK: no tail route
+  int32_t fix;                 // TSDB_PUT_FIX_DUPLICATES
+  unsigned long long* rep;     // [PR_SLOTS] counts zeroed, refusal slots all ones, by the caller
+};
+hipError_t launch_put(const PutParams& p, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

@@ -45,6 +45,7 @@ enum Opt : int {
   OPT_APPEND_RESERVE, // tsdbhip_append grows the blobs to need x (1 + this / 100); unset: 50; 0: an exact fit (every append grows)
   OPT_REGULAR,        // 0: the regular tile lists through the ordinary k_fast (qualifiers read); A/B runs and parity tests
   OPT_LAST_WALK,      // 1: every tsdbhip_last answer through the walk kernel k_last_walk (parity tests, A/B runs)
+  OPT_PUT_WALK,       // 1: every resident row a tsdbhip_put rewrites through k_put's walked route (parity tests, A/B runs)
   OPT_TRACE,          // 1: host wall time of load / query phases on stderr (tsdbhip_append: its stages by hipEvents)
   OPT_DBG,            // profiling bits (results invalid); honoured only by a -DTSDBHIP_KDBG build
   OPT_COUNT

@@ -37,14 +37,14 @@ EXPORTS = [
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
     "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
-    "tsdbhip_remove", "tsdbhip_last",
+    "tsdbhip_remove", "tsdbhip_last", "tsdbhip_put",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
 OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "TRACE", "DBG"]
+           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TRACE", "DBG"]
 
 IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
@@ -125,6 +125,7 @@ def lib():
         L.tsdbhip_trim.argtypes =[vp, C.c_int64, C.c_int32, C.POINTER(abi.TrimInfo)]
         L.tsdbhip_remove.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_int32, vp, C.POINTER(abi.RemoveInfo)]
         L.tsdbhip_last.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(abi.LastInfo)]
+        L.tsdbhip_put.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.POINTER(abi.PutInfo)]
         L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
@@ -418,6 +419,21 @@ class Engine:
         info = abi.UpsertInfo()
         _check(lib().tsdbhip_upsert(self.ctx, C.byref(delta.c), idx.ctypes.data if len(idx) else None,
                                     new.ctypes.data if len(new) else None, C.byref(info)))
+        return info
+
+    def put(self, points, fix_duplicates: bool = False) -> abi.PutInfo:
+        """tsdbhip_put: datapoint writes merged into the resident rows on the device, as a scan of
+        the store after the same TSDB.addPoint calls would compact them.  points: in write order, an
+        abi.POINT_DTYPE array or [(series_index, timestamp, kind, value), ...] (abi.make_points);
+        series_index is a batch index in the present numbering, of a resident series."""
+        if not (isinstance(points, np.ndarray) and points.dtype == abi.POINT_DTYPE):
+            points = abi.make_points(points)
+        pts = np.ascontiguousarray(points)
+        if pts.ndim != 1:
+            raise ValueError("points must be one-dimensional")
+        info = abi.PutInfo()
+        _check(lib().tsdbhip_put(self.ctx, pts.ctypes.data if len(pts) else None, len(pts),
+                                 abi.PUT_FIX_DUPLICATES if fix_duplicates else 0, C.byref(info)))
         return info
 
     def trim(self, cutoff_s: int, pack_dead_pct: int = abi.TRIM_NO_PACK) -> abi.TrimInfo:

@@ -700,6 +700,56 @@ class ResidentSpans:
         self.span_keys = merged_keys
         return info
 
+    def put(self, points):
+        """Datapoint writes (TSDB.addPoint / IncomingDataPoints.addPoint) that land in the store and
+        in the resident batch at the store's own granularity (Engine.put, tsdbhip_put): points is
+        [(tags, timestamp, kind, value), ...] in write order, kind abi.PUT_LONG / PUT_FLOAT /
+        PUT_DOUBLE.  Every point is written into the store (add_long / add_float / add_double).
+        The points of resident series whose row base lies inside the resident range then go to the
+        engine in one call, with the store's fix_duplicates, and the touched spans' rows are taken
+        from the store's compacted rows.  Hours touched by a series that is not resident yet, and
+        every hour of the call when the engine refuses it with an IllegalDataException (a
+        duplicate the store may have overwritten, a malformed resident cell, a row that failed its
+        compaction at the load) or as not implemented (a cell whose offsets do not increase), fall
+        back to refresh() over those hours -- a rescan and an upsert, which raises what the store's
+        own read of such a row raises; the store holds the points by then, so after any exception
+        the caller brings the spans up to date with refresh().  Points outside the resident range
+        only reach the store.  Returns (abi.PutInfo or None, [abi.UpsertInfo of each fallback])."""
+        from .engine import EngineError
+        from .store import base_time_of
+        add = {abi.PUT_LONG: self.store.add_long, abi.PUT_FLOAT: self.store.add_float, abi.PUT_DOUBLE: self.store.add_double}
+        index_of = {sk: i for i, sk in enumerate(self.span_keys)}
+        direct, touched, fallback = [], set(), set()
+        for tags, ts, kind, value in points:
+            add[kind](self.metric, ts, value, tags)
+            sk = self.store._series_uids(self.metric, tags)
+            base = base_time_of(ts)
+            if not self.scan_start_s <= base < self.scan_end_s:
+                continue
+            if sk in index_of:
+                direct.append((index_of[sk], ts, kind, value))
+                touched.add((sk, base))
+            else:
+                fallback.add(base)
+        info = None
+        if direct:
+            try:
+                info = self.engine.put(direct, fix_duplicates=self.store.fix_duplicates)
+            except EngineError as e:
+                if e.code not in (abi.TSDB_E_ILLEGAL_DATA, abi.TSDB_E_NOT_IMPLEMENTED):
+                    raise
+                fallback |= {base for _, base in touched}
+                touched = set()
+        for sk, base in touched:
+            if base in fallback:
+                continue   # (the rescan below brings the row)
+            i = index_of[sk]
+            by_base = {r[0]: r for r in self.spans[i][1]}
+            by_base[base] = (base,) + tuple(self.store.compact((sk[0], sk[1], base)))
+            self.spans[i] = (sk, [by_base[b] for b in sorted(by_base)])
+        upserts = [self.refresh(base, base + 3600) for base in sorted(fallback)]
+        return info, upserts
+
     def trim(self, scan_start_s: int, pack_dead_pct: int = 50):
         """Move the resident range's start to scan_start_s without a reload (Engine.trim,
         tsdbhip_trim): the rows a scan of [scan_start_s, scan_end_s) no longer returns -- those
