@@ -202,7 +202,8 @@ const char* tsdbhip_last_error(void);
  * APPEND_RESERVE (per cent of room tsdbhip_append leaves when it re-allocates the blobs; 0: an exact fit),
  * REGULAR (0: the regular tile lists through the ordinary streaming kernel, qualifiers read),
  * LAST_WALK (1: every tsdbhip_last answer through the walk kernel),
- * PUT_WALK (1: every resident row a tsdbhip_put rewrites through the walked route), TRACE, DBG
+ * PUT_WALK (1: every resident row a tsdbhip_put rewrites through the walked route),
+ * TAGS_SORT (1: tsdbhip_regroup_tags always numbers the groups by the sort route), TRACE, DBG
  * (opentsdb_amd/csrc/opts.h says what each value does).  Process-wide; -1 resets an option to
  * its production choice, which is every option's initial state.  The library reads no
  * environment variable: an inherited environment cannot change its kernels.  DBG is honoured
@@ -531,6 +532,79 @@ int tsdbhip_last(tsdbhip_ctx* ctx, const int64_t* series_index, int64_t n_sel,
                  int64_t anchor_s, const int64_t* anchor_each /* n_sel entries or NULL */,
                  int32_t back_scan, int64_t* ts_ms, uint64_t* bits, uint8_t* kind,
                  tsdbhip_last_info* info /* may be NULL */);
+/* Tag filters and group-by keys on the device: the first half of
+ * TsdbQuery.GroupByAndAggregateCB.call (src/core/TsdbQuery.java:927-1048) -- which spans a query
+ * sees and which SpanGroup each belongs to -- over a resident table of the loaded series' tags,
+ * followed by tsdbhip_regroup's work with the ids it finds.  The device never sees a string: the
+ * host resolves names, wildcards, regular expressions and case-insensitive literals over the UID
+ * dictionaries into the primitives below (INTEGRATION.md maps each TagVFilter onto them).
+ *
+ * tsdbhip_tags_load: the loaded series' tags in batch order (tsdbhip_regroup's index space,
+ * excluded series included), UIDs as unsigned integers (big-endian UID bytes read as a number;
+ * UIDs wider than 4 bytes are not supported).  The table is copied; it replaces an earlier one.
+ * It is dropped by every load entry point and by an edit that changes the series numbering (a
+ * tsdbhip_append / tsdbhip_upsert that adds a series, a tsdbhip_remove that retires one);
+ * tsdbhip_regroup, _trim, _put, _last and edits that keep the numbering keep it.
+ * tsdbhip_tags_loaded: its series and tags, 0 / 0 without a table.
+ *
+ * Filter primitives, pure predicates on a series' tag map:
+ *   TSDB_TF_ANY      the series has tagk;
+ *   TSDB_TF_IN       it has tagk and its tagv is in the set (an empty set matches nobody);
+ *   TSDB_TF_NOT_IN   it lacks tagk, or its tagv is not in the set (an empty set matches everybody);
+ *   TSDB_TF_NOT_KEY  it lacks tagk.
+ * A series is visible when every filter holds; with explicit_tags it must also have exactly the
+ * distinct tagks of the filters other than NOT_KEY and no others (QueryUtil.getRowKeyUIDRegex
+ * without its skip-any-tags parts).  Every other series gets TSDB_GROUP_EXCLUDED.  The key of a
+ * visible series is the tuple of its tagvs for group_by, in that order; a visible series that
+ * lacks one of them gets TSDB_GROUP_NONE.  The id of a key is its rank among the distinct
+ * complete keys of the visible series, ascending in the lexicographic order of the unsigned UIDs
+ * (ByteMap order of the concatenated big-endian UIDs).  n_group_by == 0: every visible series
+ * gets id 0.  Every series excluded is legal (n_groups 0).
+ *
+ * Without TSDB_TAGS_DRY the context afterwards is bit for bit what tsdbhip_regroup with these ids
+ * leaves.  With it nothing of the batch changes: only group_id, info and the keys are produced.
+ * info->route: 0 no group-by (no numbering), 1 rank (presence maps over the UIDs and over the
+ * mixed-radix composite of the column ranks: taken while the table's largest tagv UID is below
+ * 2^24 and the product of the column cardinalities is at most 2^22), 2 sort (any UIDs, any number
+ * of keys; option TAGS_SORT forces it).
+ * tsdbhip_tags_keys: the distinct keys of the last tsdbhip_regroup_tags that succeeded,
+ * [n_groups][n_group_by] tagv UIDs in group id order.
+ *
+ * TSDB_E_ILLEGAL_ARGUMENT: null pointers; n_series other than the loaded count; tag_ptr not
+ * ascending from 0; tagks not strictly ascending in a series; an unknown kind or flag bit; a set
+ * range outside [0, n_set] or not strictly ascending; group_by not strictly ascending;
+ * n_group_by > 8 (Const.MAX_NUM_TAGS) or n_filters > 64; explicit_tags other than 0 / 1.
+ * TSDB_E_ILLEGAL_STATE: tsdbhip_regroup_tags without a table, tsdbhip_tags_keys without a
+ * previous call.  TSDB_E_NOT_IMPLEMENTED: a multi-device context, a rollup batch, a shard load
+ * (tsdbhip_regroup's refusals).  Every check precedes any allocation; an error leaves the table,
+ * the grouping and the keys as they were. */
+typedef struct {
+  int64_t n_series;          /* must equal the number of loaded series */
+  const int64_t* tag_ptr;    /* [n_series + 1], from 0 */
+  const uint32_t* tagk;      /* [tag_ptr[n_series]] strictly ascending inside a series (row-key order) */
+  const uint32_t* tagv;
+} tsdbhip_tag_table;
+int tsdbhip_tags_load(tsdbhip_ctx* ctx, const tsdbhip_tag_table* table);
+int tsdbhip_tags_loaded(tsdbhip_ctx* ctx, int64_t* n_series, int64_t* n_tags);
+enum { TSDB_TF_ANY = 0, TSDB_TF_IN, TSDB_TF_NOT_IN, TSDB_TF_NOT_KEY };
+typedef struct { uint32_t tagk; int32_t kind; int64_t set_begin, set_end; } tsdbhip_tag_filter;
+typedef struct {
+  int32_t n_filters;  const tsdbhip_tag_filter* filters;   /* ANDed; several on one tagk allowed */
+  int64_t n_set;      const uint32_t* tagv_set;            /* each [set_begin, set_end) strictly ascending */
+  int32_t n_group_by; const uint32_t* group_by;            /* tagk UIDs, strictly ascending; 0: one group */
+  int32_t explicit_tags;
+} tsdbhip_tag_query;
+#define TSDB_TAGS_DRY 1u     /* compute and report, do not regroup */
+typedef struct {
+  int64_t visible, excluded, ungrouped, n_groups;   /* visible counts the ungrouped too */
+  int32_t route;             /* 0 no group-by, 1 rank, 2 sort */
+  int32_t regrouped;         /* the batch was regrouped (no TSDB_TAGS_DRY) */
+  int64_t table_bytes;       /* bytes of the tag table the match pass reads */
+  double kernel_ms;          /* hipEvent time of the tag kernels, without the regroup that follows */
+} tsdbhip_tags_info;
+int tsdbhip_regroup_tags(tsdbhip_ctx* ctx, const tsdbhip_tag_query* query, uint32_t flags,
+                         int32_t* group_id /* [N] batch order, may be NULL */, tsdbhip_tags_info* info /* may be NULL */);
+int tsdbhip_tags_keys(tsdbhip_ctx* ctx, uint32_t* keys);
 /* ---- sharding one query's spans over ranks -------------------------
  * Byte-balanced contiguous shards, one per rank; bounds[world + 1], rank r owns
  * [bounds[r], bounds[r + 1]) of:

@@ -363,6 +363,101 @@ class LastInfo(C.Structure):
 
 LAST_NONE, LAST_INT, LAST_FLOAT = 0, 1, 2    # tsdbhip_last's kind[i]
 
+# tsdbhip_regroup_tags: the filter primitives (tsdbhip.h TSDB_TF_*), its flag, info.route
+TF_ANY, TF_IN, TF_NOT_IN, TF_NOT_KEY = 0, 1, 2, 3
+TAGS_DRY = 1
+TAGS_ROUTE_NOGROUP, TAGS_ROUTE_RANK, TAGS_ROUTE_SORT = 0, 1, 2
+TAGS_MAX_GROUP_BY, TAGS_MAX_FILTERS = 8, 64
+
+
+class TagTable(C.Structure):
+    """tsdbhip_tag_table: the loaded series' tags in batch order."""
+    _fields_ = [
+        ("n_series", C.c_int64),
+        ("tag_ptr", C.c_void_p),
+        ("tagk", C.c_void_p),
+        ("tagv", C.c_void_p),
+    ]
+
+
+class TagFilter(C.Structure):
+    """tsdbhip_tag_filter: one primitive, its set tagv_set[set_begin:set_end]."""
+    _fields_ = [
+        ("tagk", C.c_uint32),
+        ("kind", C.c_int32),
+        ("set_begin", C.c_int64),
+        ("set_end", C.c_int64),
+    ]
+
+
+class TagQuery(C.Structure):
+    """tsdbhip_tag_query."""
+    _fields_ = [
+        ("n_filters", C.c_int32),
+        ("filters", C.c_void_p),
+        ("n_set", C.c_int64),
+        ("tagv_set", C.c_void_p),
+        ("n_group_by", C.c_int32),
+        ("group_by", C.c_void_p),
+        ("explicit_tags", C.c_int32),
+    ]
+
+
+class TagsInfo(C.Structure):
+    """tsdbhip_tags_info: what a tsdbhip_regroup_tags found and how it numbered the groups."""
+    _fields_ = [
+        ("visible", C.c_int64),
+        ("excluded", C.c_int64),
+        ("ungrouped", C.c_int64),
+        ("n_groups", C.c_int64),
+        ("route", C.c_int32),
+        ("regrouped", C.c_int32),
+        ("table_bytes", C.c_int64),
+        ("kernel_ms", C.c_double),
+    ]
+
+
+class HostTagQuery:
+    """A tag query as data: filters [(tagk uid, abi.TF_*, ascending tagv uids)], the group-by tagk
+    uids (ascending) and explicit_tags; .c is the tsdbhip_tag_query over arrays this object owns."""
+
+    def __init__(self, filters, group_by, explicit_tags=False):
+        self.filter_list = [(int(k), int(kind), [int(v) for v in vs]) for k, kind, vs in filters]
+        self.group_by_list = [int(k) for k in group_by]
+        self.explicit_tags = bool(explicit_tags)
+        n = len(self.filter_list)
+        self.filters = (TagFilter * max(1, n))()
+        sets = []
+        for i, (k, kind, vs) in enumerate(self.filter_list):
+            self.filters[i] = TagFilter(k, kind, len(sets), len(sets) + len(vs))
+            sets += vs
+        self.sets = np.asarray(sets, dtype=np.uint32)
+        self.group_by = np.asarray(self.group_by_list, dtype=np.uint32)
+        self.c = TagQuery(n, C.cast(self.filters, C.c_void_p) if n else None,
+                          len(self.sets), self.sets.ctypes.data if len(self.sets) else None,
+                          len(self.group_by), self.group_by.ctypes.data if len(self.group_by) else None,
+                          int(self.explicit_tags))
+
+    def __eq__(self, other):
+        return isinstance(other, HostTagQuery) and (self.filter_list, self.group_by_list, self.explicit_tags) == \
+            (other.filter_list, other.group_by_list, other.explicit_tags)
+
+    def __repr__(self):
+        return f"HostTagQuery({self.filter_list}, {self.group_by_list}, explicit_tags={self.explicit_tags})"
+
+
+def tag_table_arrays(tag_rows):
+    """(tag_ptr int64, tagk uint32, tagv uint32) of [[(tagk uid, tagv uid), ...] a series, ...]:
+    each series' tags by ascending tagk, the row key's order."""
+    ptr = np.zeros(len(tag_rows) + 1, np.int64)
+    ks, vs = [], []
+    for i, tags in enumerate(tag_rows):
+        for k, v in sorted(tags):
+            ks.append(k)
+            vs.append(v)
+        ptr[i + 1] = len(ks)
+    return ptr, np.asarray(ks, np.uint32), np.asarray(vs, np.uint32)
+
 
 def new_query(start_time: int, end_time: int, aggregator: str | int = "sum", *,
               ds_function: int = -1, ds_interval_ms: int = 0, ds_fill: int = FILL_NONE,

@@ -437,6 +437,18 @@ struct tsdbhip_ctx {
   // tsdbhip_put: the surviving puts, the delta rows, k_put's report
   DevBuf pt_pts, pt_rows, pt_rep;
   HostBuf pt_stage;                    // ... page-locked (the puts, then the rows, then the report read back)
+  // tsdbhip_tags_load / tsdbhip_regroup_tags: the resident tag table (tag_ptr, then one (tagk, tagv)
+  // pair a tag), the query as the device reads it, the ids, the key words, the numbering's scratch
+  // (TagsParams says which route uses which), the keys of the last call and of the one in flight,
+  // the device's report; dropped with the table (drop_tags)
+  bool tg_loaded = false;
+  int64_t tg_n = 0, tg_tags = 0;
+  uint32_t tg_max_tagv = 0;
+  DevBuf tg_ptr, tg_pairs, tg_q, tg_ids, tg_kw, tg_s[6], tg_keys, tg_keys2, tg_meta;
+  HostBuf tg_stage;                    // ... page-locked (the query up; the report and the ids back)
+  bool tg_have_keys = false;
+  int64_t tg_n_groups = 0;
+  int32_t tg_n_gb = 0;
   std::vector<int32_t> h_pos;
   bool last_pos_valid = false;
   std::vector<int64_t> h_srp;          // [n_series+1]
@@ -683,7 +695,7 @@ const char* const kOptNames[OPT_COUNT] = {
     "FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
     "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
     "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TRACE", "DBG"};
+    "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TAGS_SORT", "TRACE", "DBG"};
 int opt_index(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < OPT_COUNT; i++)
@@ -885,7 +897,22 @@ static void invalidate_derived(tsdbhip_ctx* c) {
   c->ro_n = 0;
 }
 
+// The resident tag table goes with the series numbering it was loaded for: every load, and an edit
+// that adds or retires a series.  A context that never loaded one has nothing to release.
+static void drop_tags(tsdbhip_ctx* c) {
+  if (!c->tg_loaded && !c->tg_have_keys) return;
+  for (DevBuf* b : {&c->tg_ptr, &c->tg_pairs, &c->tg_q, &c->tg_ids, &c->tg_kw, &c->tg_s[0], &c->tg_s[1], &c->tg_s[2], &c->tg_s[3],
+                    &c->tg_s[4], &c->tg_s[5], &c->tg_keys, &c->tg_keys2, &c->tg_meta})
+    b->release();
+  c->tg_stage.release();
+  c->tg_loaded = c->tg_have_keys = false;
+  c->tg_n = c->tg_tags = c->tg_n_groups = 0;
+  c->tg_max_tagv = 0;
+  c->tg_n_gb = 0;
+}
+
 static void release_batch(tsdbhip_ctx* c) {
+  drop_tags(c);
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
                     &c->n_tb, &c->n_te, &c->n_tg, &c->n_gtp, &c->rows2, &c->srp2, &c->gid2, &c->rg_ent, &c->ap_rows, &c->ap_ent, &c->ap_touch,
                     &c->reg, &c->reg2, &c->ap_reg, &c->tr_skip, &c->tr_list, &c->tr_ser, &c->tr_rows, &c->tr_reg, &c->tr_qdst,
@@ -2860,12 +2887,17 @@ static int reindex_suspects(tsdbhip_ctx* c, IndexPlan& ip, const int64_t* sus, i
 // would have given them -- group ascending, then the ungrouped, batch order inside each -- with
 // the excluded series behind; no cell byte moves and nothing is re-indexed.  group_id is in
 // batch order, the index space of h_orig.
+//
+// regroup_apply is the call after its checks, shared with tsdbhip_regroup_tags: the caller holds
+// the lock and hands over valid ids of every loaded series (at least one) and the largest of them.
+static int regroup_apply(tsdbhip_ctx* c, const int32_t* group_id, int32_t maxg);
+
 extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t n_series) {
   if (!c || !group_id) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
   MD_REFUSE(c, "tsdbhip_regroup");
   CtxLock lk(c);
   if (c->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_regroup over a rollup batch (tsdbhip_load_rollup)");
-  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
+  const int64_t N = c->n_series_loaded;
   if (!c->regroup_ok && (N > 0 || n_series != 0))
     return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_regroup needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "
                                         "tsdbhip_synth (a shard's groups are numbered globally)");
@@ -2878,6 +2910,11 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
     maxg = std::max(maxg, group_id[s]);
   }
   if (N == 0) return 0;
+  return regroup_apply(c, group_id, maxg);
+}
+
+static int regroup_apply(tsdbhip_ctx* c, const int32_t* group_id, int32_t maxg) {
+  const int64_t N = c->n_series_loaded, NR = c->n_rows_loaded;
   HIP_OK(hipSetDevice(c->device));
   const int64_t G = (int64_t)maxg + 1;
   // the new order of the current resident positions (pos: batch index -> current position)
@@ -2928,6 +2965,252 @@ extern "C" int tsdbhip_regroup(tsdbhip_ctx* c, const int32_t* group_id, int64_t 
   m.commit(c, &order);
   invalidate_derived(c);
   return finish_classes(c);
+}
+
+// ---- tag filters and group-by keys on the device (k_tags.hip) ----------------
+// the contexts tsdbhip_regroup refuses, for the tag entry points
+#define TAGS_CTX_REFUSE(c, fn)                                                                                        \
+  if ((c)->ro_active) return fail(TSDB_E_NOT_IMPLEMENTED, fn " over a rollup batch (tsdbhip_load_rollup)");           \
+  if (!(c)->regroup_ok && (c)->n_series_loaded > 0)                                                                   \
+  return fail(TSDB_E_NOT_IMPLEMENTED, fn " needs a batch loaded by tsdbhip_load, tsdbhip_load_cells or "              \
+                                         "tsdbhip_synth (a shard's groups are numbered globally)")
+
+extern "C" int tsdbhip_tags_load(tsdbhip_ctx* c, const tsdbhip_tag_table* t) {
+  if (!c || !t) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_tags_load");
+  CtxLock lk(c);
+  TAGS_CTX_REFUSE(c, "tsdbhip_tags_load");
+  const int64_t N = c->n_series_loaded;
+  if (t->n_series != N)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_series is " + std::to_string(t->n_series) + ", the loaded batch has " +
+                                             std::to_string(N) + " series");
+  if (!t->tag_ptr) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null tag_ptr");
+  if (t->tag_ptr[0] != 0) return fail(TSDB_E_ILLEGAL_ARGUMENT, "tag_ptr does not start at 0");
+  for (int64_t s = 0; s < N; s++)
+    if (t->tag_ptr[s + 1] < t->tag_ptr[s]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "tag_ptr is not ascending");
+  const int64_t T = t->tag_ptr[N];
+  if (T > 0 && (!t->tagk || !t->tagv)) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null tagk / tagv");
+  uint32_t max_tagv = 0;
+  for (int64_t s = 0; s < N; s++)
+    for (int64_t e = t->tag_ptr[s]; e < t->tag_ptr[s + 1]; e++) {
+      if (e > t->tag_ptr[s] && t->tagk[e] <= t->tagk[e - 1])
+        return fail(TSDB_E_ILLEGAL_ARGUMENT, "the tagks of series " + std::to_string(s) + " are not strictly ascending");
+      max_tagv = std::max(max_tagv, t->tagv[e]);
+    }
+  HIP_OK(hipSetDevice(c->device));
+  // the new table beside the old one, which stays until both copies are over
+  DevBuf ptr, pairs;
+  struct Hold { DevBuf &a, &b; ~Hold() { a.release(); b.release(); } } hold{ptr, pairs};
+  HIP_OK(ptr.ensure((size_t)(N + 1) * 8));
+  HIP_OK(pairs.ensure(std::max<size_t>(1, (size_t)T) * sizeof(uint2)));
+  std::vector<uint2> hp((size_t)T);
+  for (int64_t e = 0; e < T; e++) hp[e] = make_uint2(t->tagk[e], t->tagv[e]);
+  HIP_OK(hipMemcpyAsync(ptr.p, t->tag_ptr, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (T) HIP_OK(hipMemcpyAsync(pairs.p, hp.data(), (size_t)T * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  std::swap(c->tg_ptr, ptr);
+  std::swap(c->tg_pairs, pairs);
+  c->tg_loaded = true;
+  c->tg_n = N;
+  c->tg_tags = T;
+  c->tg_max_tagv = max_tagv;
+  c->tg_have_keys = false;   // (the keys belong to the table they were read from)
+  return 0;
+}
+
+extern "C" int tsdbhip_tags_loaded(tsdbhip_ctx* c, int64_t* n_series, int64_t* n_tags) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  MD_REFUSE(c, "tsdbhip_tags_loaded");
+  CtxLock lk(c);
+  if (n_series) *n_series = c->tg_loaded ? c->tg_n : 0;
+  if (n_tags) *n_tags = c->tg_loaded ? c->tg_tags : 0;
+  return 0;
+}
+
+extern "C" int tsdbhip_regroup_tags(tsdbhip_ctx* c, const tsdbhip_tag_query* q, uint32_t flags, int32_t* group_id,
+                                    tsdbhip_tags_info* info) {
+  if (!c || !q) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  MD_REFUSE(c, "tsdbhip_regroup_tags");
+  CtxLock lk(c);
+  TAGS_CTX_REFUSE(c, "tsdbhip_regroup_tags");
+  // ---- the query: every check before any allocation ----
+  if (flags & ~TSDB_TAGS_DRY) return fail(TSDB_E_ILLEGAL_ARGUMENT, "unknown flag bits");
+  if (q->explicit_tags != 0 && q->explicit_tags != 1) return fail(TSDB_E_ILLEGAL_ARGUMENT, "explicit_tags is 0 or 1");
+  if (q->n_filters < 0 || q->n_filters > TAGS_MAX_FILTERS)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_filters outside [0, " + std::to_string(TAGS_MAX_FILTERS) + "]");
+  if (q->n_group_by < 0 || q->n_group_by > TAGS_MAX_GROUP_BY)
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_group_by outside [0, " + std::to_string(TAGS_MAX_GROUP_BY) + "] (Const.MAX_NUM_TAGS)");
+  if (q->n_set < 0 || q->n_set > (int64_t)UINT32_MAX) return fail(TSDB_E_ILLEGAL_ARGUMENT, "n_set outside [0, 2^32)");
+  if ((q->n_filters && !q->filters) || (q->n_set && !q->tagv_set) || (q->n_group_by && !q->group_by))
+    return fail(TSDB_E_ILLEGAL_ARGUMENT, "null argument");
+  for (int f = 0; f < q->n_filters; f++) {
+    const tsdbhip_tag_filter& t = q->filters[f];
+    if (t.kind < TSDB_TF_ANY || t.kind > TSDB_TF_NOT_KEY) return fail(TSDB_E_ILLEGAL_ARGUMENT, "unknown filter kind");
+    if (t.set_begin < 0 || t.set_end < t.set_begin || t.set_end > q->n_set)
+      return fail(TSDB_E_ILLEGAL_ARGUMENT, "a filter's set range lies outside [0, n_set]");
+    for (int64_t e = t.set_begin + 1; e < t.set_end; e++)
+      if (q->tagv_set[e] <= q->tagv_set[e - 1]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "a filter's set is not strictly ascending");
+  }
+  for (int j = 1; j < q->n_group_by; j++)
+    if (q->group_by[j] <= q->group_by[j - 1]) return fail(TSDB_E_ILLEGAL_ARGUMENT, "group_by is not strictly ascending");
+  if (!c->tg_loaded) return fail(TSDB_E_ILLEGAL_STATE, "tsdbhip_regroup_tags without a tag table (tsdbhip_tags_load)");
+  const int64_t N = c->n_series_loaded;
+  if (N != c->tg_n) return fail(TSDB_E_ILLEGAL_STATE, "tsdbhip_regroup_tags: the tag table is not the loaded series' (internal)");
+  if (N >= INT32_MAX) return fail(TSDB_E_NOT_IMPLEMENTED, "tsdbhip_regroup_tags over 2^31 - 1 series or more");
+  const int ngb = q->n_group_by;
+  const bool dry = (flags & TSDB_TAGS_DRY) != 0;
+  tsdbhip_tags_info ti{};
+  ti.table_bytes = (N + 1) * 8 + c->tg_tags * (int64_t)sizeof(uint2);
+  int route = ngb == 0 ? TAGS_ROUTE_NOGROUP
+              : opt_is(OPT_TAGS_SORT, 1) || (int64_t)c->tg_max_tagv >= TAGS_RANK_UID_LIMIT ? TAGS_ROUTE_SORT : TAGS_ROUTE_RANK;
+  if (N == 0) {
+    ti.route = route;
+    if (info) *info = ti;
+    return 0;
+  }
+  HIP_OK(hipSetDevice(c->device));
+  // the tagks an explicit_tags series must have: those of the filters other than NOT_KEY, once each
+  std::vector<uint32_t> etagk;
+  if (q->explicit_tags) {
+    for (int f = 0; f < q->n_filters; f++)
+      if (q->filters[f].kind != TSDB_TF_NOT_KEY) etagk.push_back(q->filters[f].tagk);
+    std::sort(etagk.begin(), etagk.end());
+    etagk.erase(std::unique(etagk.begin(), etagk.end()), etagk.end());
+  }
+  // ---- the page-locked stage: the query up, the report and the ids back ----
+  const size_t o_set = (size_t)q->n_filters * sizeof(TagFilterDev), o_gb = o_set + (size_t)q->n_set * 4,
+               o_et = o_gb + (size_t)ngb * 4, q_bytes = o_et + etagk.size() * 4, o_meta = (q_bytes + 63) / 64 * 64,
+               o_ids = o_meta + 64;
+  static_assert(sizeof(TagsMeta) <= 64, "TagsMeta fits its slot of the stage");
+  HIP_OK(c->tg_stage.ensure(o_ids + (size_t)N * 4));
+  uint8_t* const st = static_cast<uint8_t*>(c->tg_stage.p);
+  TagFilterDev* const hf = reinterpret_cast<TagFilterDev*>(st);
+  for (int f = 0; f < q->n_filters; f++)
+    hf[f] = TagFilterDev{q->filters[f].tagk, q->filters[f].kind, (uint32_t)q->filters[f].set_begin, (uint32_t)q->filters[f].set_end};
+  if (q->n_set) std::memcpy(st + o_set, q->tagv_set, (size_t)q->n_set * 4);
+  if (ngb) std::memcpy(st + o_gb, q->group_by, (size_t)ngb * 4);
+  if (!etagk.empty()) std::memcpy(st + o_et, etagk.data(), etagk.size() * 4);
+  // ---- allocations ----
+  const int64_t W = ((int64_t)c->tg_max_tagv >> 5) + 1;   // presence words a column
+  HIP_OK(c->tg_q.ensure(std::max<size_t>(q_bytes, 16)));
+  HIP_OK(c->tg_ids.ensure((size_t)N * 4));
+  HIP_OK(c->tg_kw.ensure(std::max<size_t>(1, (size_t)ngb) * N * 4));
+  HIP_OK(c->tg_keys2.ensure(std::max<size_t>(1, (size_t)ngb) * N * 4));
+  HIP_OK(c->tg_meta.ensure(sizeof(TagsMeta)));
+  auto ensure_route = [&](int r) -> hipError_t {
+    hipError_t e = hipSuccess;
+    if (r == TAGS_ROUTE_RANK) {
+      const size_t sz[5] = {(size_t)ngb * W * 4, ((size_t)ngb * W + 1) * 4, (size_t)N * 4, (size_t)(TAGS_RANK_MAX_KEYS + 1) * 4,
+                            (size_t)(TAGS_RANK_MAX_KEYS + 1) * 4};
+      for (int i = 0; i < 5 && e == hipSuccess; i++) e = c->tg_s[i].ensure(sz[i]);
+    } else if (r == TAGS_ROUTE_SORT) {
+      for (int i = 0; i < 6 && e == hipSuccess; i++) e = c->tg_s[i].ensure((size_t)N * 4);
+    }
+    return e;
+  };
+  HIP_OK(ensure_route(route));
+  // ---- queued work ----
+  TagsParams p{};
+  auto fill = [&](int r) {
+    p.tag_ptr = c->tg_ptr.as<int64_t>();
+    p.pairs = c->tg_pairs.as<uint2>();
+    p.n_series = N;
+    const uint8_t* const dq = c->tg_q.as<uint8_t>();
+    p.filters = reinterpret_cast<const TagFilterDev*>(dq);
+    p.n_filters = q->n_filters;
+    p.sets = reinterpret_cast<const uint32_t*>(dq + o_set);
+    p.group_by = reinterpret_cast<const uint32_t*>(dq + o_gb);
+    p.n_group_by = ngb;
+    p.etagk = reinterpret_cast<const uint32_t*>(dq + o_et);
+    p.n_etagk = (int32_t)etagk.size();
+    p.explicit_tags = q->explicit_tags;
+    p.ids = c->tg_ids.as<int32_t>();
+    p.kw = c->tg_kw.as<uint32_t>();
+    p.keys = c->tg_keys2.as<uint32_t>();
+    p.meta = c->tg_meta.as<TagsMeta>();
+    p.pres = p.wrank = p.comp = p.cpres = p.crank = nullptr;
+    p.ka = p.kb = p.pa = p.pb = p.head = p.hsum = nullptr;
+    p.W = W;
+    if (r == TAGS_ROUTE_RANK) {
+      p.pres = c->tg_s[0].as<uint32_t>();
+      p.wrank = c->tg_s[1].as<uint32_t>();
+      p.comp = c->tg_s[2].as<uint32_t>();
+      p.cpres = c->tg_s[3].as<uint32_t>();
+      p.crank = c->tg_s[4].as<uint32_t>();
+    } else if (r == TAGS_ROUTE_SORT) {
+      p.ka = c->tg_s[0].as<uint32_t>();
+      p.kb = c->tg_s[1].as<uint32_t>();
+      p.pa = c->tg_s[2].as<uint32_t>();
+      p.pb = c->tg_s[3].as<uint32_t>();
+      p.head = c->tg_s[4].as<uint32_t>();
+      p.hsum = c->tg_s[5].as<uint32_t>();
+    }
+  };
+  fill(route);
+  const TagsMeta* const hm = reinterpret_cast<const TagsMeta*>(st + o_meta);
+  const int32_t* const ids = reinterpret_cast<const int32_t*>(st + o_ids);
+  auto download = [&]() -> hipError_t {
+    hipError_t e = hipEventRecord(c->ev[1], c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(st + o_meta, c->tg_meta.p, sizeof(TagsMeta), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(st + o_ids, c->tg_ids.p, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e;
+  };
+  if (q_bytes) HIP_OK(hipMemcpyAsync(c->tg_q.p, st, q_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipMemsetAsync(c->tg_meta.p, 0, sizeof(TagsMeta), c->stream));
+  HIP_OK(hipEventRecord(c->ev[0], c->stream));
+  if (route == TAGS_ROUTE_RANK) {
+    HIP_OK(hipMemsetAsync(p.pres, 0, (size_t)ngb * W * 4, c->stream));
+    HIP_OK(hipMemsetAsync(p.cpres, 0, (size_t)(TAGS_RANK_MAX_KEYS + 1) * 4, c->stream));
+  }
+  HIP_OK(launch_tags_match(p, c->stream));
+  if (route == TAGS_ROUTE_RANK) HIP_OK(tags_number_rank(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  if (route == TAGS_ROUTE_SORT) HIP_OK(tags_number_sort(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(download());   // the one synchronisation
+  if (route == TAGS_ROUTE_RANK && !hm->rank_ok) {
+    // more composite keys than the rank route's map holds: the verdicts and the key words stand, the
+    // sort route numbers them (a second wait, on this path only)
+    route = TAGS_ROUTE_SORT;
+    HIP_OK(ensure_route(route));
+    fill(route);
+    HIP_OK(tags_number_sort(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(download());
+  }
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+  for (int64_t s = 0; s < N; s++) {
+    if (ids[s] == TSDB_GROUP_EXCLUDED) ti.excluded++;
+    else if (ids[s] == TSDB_GROUP_NONE) ti.ungrouped++;
+  }
+  ti.visible = N - ti.excluded;
+  ti.n_groups = ngb == 0 ? (ti.visible > 0 ? 1 : 0) : (int64_t)hm->n_groups;
+  ti.route = route;
+  ti.kernel_ms = ms;
+  if (!dry) {
+    if (const int rc = regroup_apply(c, ids, (int32_t)ti.n_groups - 1)) return rc;
+    ti.regrouped = 1;
+  }
+  if (group_id) std::memcpy(group_id, ids, (size_t)N * 4);
+  std::swap(c->tg_keys, c->tg_keys2);
+  c->tg_have_keys = true;
+  c->tg_n_groups = ti.n_groups;
+  c->tg_n_gb = ngb;
+  if (info) *info = ti;
+  return 0;
+}
+
+extern "C" int tsdbhip_tags_keys(tsdbhip_ctx* c, uint32_t* keys) {
+  if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
+  MD_REFUSE(c, "tsdbhip_tags_keys");
+  CtxLock lk(c);
+  if (!c->tg_have_keys) return fail(TSDB_E_ILLEGAL_STATE, "tsdbhip_tags_keys without a previous tsdbhip_regroup_tags");
+  const size_t n = (size_t)c->tg_n_groups * (size_t)c->tg_n_gb;
+  if (n == 0) return 0;
+  if (!keys) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null keys");
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(hipMemcpyAsync(keys, c->tg_keys.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // Newly scanned rows appended to the resident batch.  The delta's cells go to
@@ -3386,6 +3669,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   c->idx_fused = ip.fused;
   c->index_ms = t_index + t_sus;
   invalidate_derived(c);
+  if (K) drop_tags(c);   // (the numbering changed)
   mi->series_added = K;
   mi->rows_added = DR - n_repl;
   mi->rows_replaced = n_repl;
@@ -4233,6 +4517,7 @@ extern "C" int tsdbhip_remove(tsdbhip_ctx* c, const tsdbhip_remove_range* ranges
   c->idx_fused = n_sus ? ip.fused : false;
   c->index_ms = t_index;
   invalidate_derived(c);
+  if (dropped) drop_tags(c);   // (the numbering changed)
   const int rc = finish_classes(c);
   if (dropped) {
     for (int64_t b = 0; new_index && b < N; b++) new_index[b] = new_of[b];

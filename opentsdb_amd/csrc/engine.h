@@ -714,6 +714,63 @@ struct PutParams {
   unsigned long long* rep;     // [PR_SLOTS] counts zeroed, refusal slots all ones, by the caller
 };
 hipError_t launch_put(const PutParams& p, hipStream_t s);
+// tsdbhip_regroup_tags (k_tags.hip): tag filters, group keys and their dense numbering over the
+// resident tag table.
+enum : int { TAGS_ROUTE_NOGROUP = 0, TAGS_ROUTE_RANK = 1, TAGS_ROUTE_SORT = 2 };   // tsdbhip_tags_info.route
+// The rank route's limits: a presence bit per UID below TAGS_RANK_UID_LIMIT (3-byte UIDs, the
+// width tsd.storage.uid.width.tagv defaults to: 2 MB of bits a group-by column), and a presence
+// word per composite key up to TAGS_RANK_MAX_KEYS (16 MB of words, scanned once a call).
+constexpr int64_t TAGS_RANK_UID_LIMIT = 1 << 24;   // the table's largest tagv UID must be below
+constexpr int64_t TAGS_RANK_MAX_KEYS = 1 << 22;    // the product of the column cardinalities may reach it
+constexpr int TAGS_MAX_GROUP_BY = 8;               // Const.MAX_NUM_TAGS
+constexpr int TAGS_MAX_FILTERS = 64;
+struct TagFilterDev {
+  uint32_t tagk;
+  int32_t kind;        // TSDB_TF_*
+  uint32_t set_begin, set_end;   // in TagsParams.sets (below 2^32 entries)
+};
+struct TagsMeta {      // written by the device, read back with the ids
+  uint32_t mult[TAGS_MAX_GROUP_BY];   // rank route: the mixed-radix weight of each column
+  uint32_t rank_ok;    // rank route: the composite space fits TAGS_RANK_MAX_KEYS
+  uint32_t n_groups;
+};
+struct TagsParams {
+  const int64_t* tag_ptr;      // [n_series + 1]
+  const uint2* pairs;          // [tag_ptr[n_series]] (tagk, tagv), tagk ascending inside a series
+  int64_t n_series;
+  const TagFilterDev* filters;
+  int32_t n_filters;
+  const uint32_t* sets;        // the filters' tagv sets, each ascending
+  const uint32_t* group_by;    // [n_group_by] tagks, ascending
+  int32_t n_group_by;
+  const uint32_t* etagk;       // explicit_tags: the tagks a visible series must have, ascending
+  int32_t n_etagk;
+  int32_t explicit_tags;
+  int32_t* ids;                // [n_series] out: the verdict (0 complete key, TSDB_GROUP_NONE, TSDB_GROUP_EXCLUDED), then the ids
+  uint32_t* kw;                // [n_group_by][n_series] the key words of the series with a complete key
+  // rank route
+  uint32_t* pres;              // [n_group_by][W] presence bits of the columns' tagvs (null: the sort route)
+  uint32_t* wrank;             // [n_group_by * W + 1] set bits before each word
+  int64_t W;
+  uint32_t* comp;              // [n_series] composite keys
+  uint32_t* cpres;             // [TAGS_RANK_MAX_KEYS + 1] presence words of the composites, then their ranks in crank
+  uint32_t* crank;
+  // sort route
+  uint32_t* ka;                // [n_series] x 2: one column's words in the present order, double-buffered
+  uint32_t* kb;
+  uint32_t* pa;                // [n_series] x 2: the order
+  uint32_t* pb;
+  uint32_t* head;              // [n_series] first of its key, then the inclusive scan of that in hsum
+  uint32_t* hsum;
+  uint32_t* keys;              // [groups][n_group_by] out: the distinct keys in id order
+  TagsMeta* meta;
+};
+// the verdicts and key words; the rank route's presence bits when p.pres
+hipError_t launch_tags_match(const TagsParams& p, hipStream_t s);
+// the numbering, queued after launch_tags_match without a synchronisation in between; tmp: hipCUB's
+// temporary storage, grown on demand
+hipError_t tags_number_rank(const TagsParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
+hipError_t tags_number_sort(const TagsParams& p, void** tmp, size_t* tmp_bytes, hipStream_t s);
 // each series' first datapoint >= t0 in rows with base in [ss, se) (INT64_MAX: none)
 // ---- query-time compaction (k_compact.hip) ----------------------------
 enum : uint32_t { CMP_IGNORE = 0, CMP_DATA = 1, CMP_APPEND = 2 };

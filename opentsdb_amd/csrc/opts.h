@@ -46,7 +46,8 @@ enum Opt : int {
   OPT_REGULAR,        // 0: the regular tile lists through the ordinary k_fast (qualifiers read); A/B runs and parity tests
   OPT_LAST_WALK,      // 1: every tsdbhip_last answer through the walk kernel k_last_walk (parity tests, A/B runs)
   OPT_PUT_WALK,       // 1: every resident row a tsdbhip_put rewrites through k_put's walked route (parity tests, A/B runs)
-  OPT_TRACE,          // 1: host wall time of load / query phases on stderr (tsdbhip_append: its stages by hipEvents)
+  OPT_TAGS_SORT,      // 1: tsdbhip_regroup_tags numbers the groups by the sort route whatever the UIDs (parity tests, A/B runs)
+  OPT_TRACE,      // 1: host wall time of load / query phases on stderr (tsdbhip_append: its stages by hipEvents)
   OPT_DBG,            // profiling bits (results invalid); honoured only by a -DTSDBHIP_KDBG build
   OPT_COUNT
 };

@@ -38,13 +38,14 @@ EXPORTS = [
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
     "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
     "tsdbhip_remove", "tsdbhip_last", "tsdbhip_put",
+    "tsdbhip_tags_load", "tsdbhip_tags_loaded", "tsdbhip_regroup_tags", "tsdbhip_tags_keys",
 ]
 
 # developer options (tsdbhip_set_option, opentsdb_amd/csrc/opts.h)
 OPTIONS = ["FAST", "SHORT", "ROWS", "HWIN", "SEQ", "SEQ_ROWS", "SEQ_WAVE", "INDEX_GENERIC", "INDEX_FUSED", "CMP_CHUNK", "CMP_ROWS",
            "CMP_ONEPASS", "PCT_ROWS", "PCT_KEYS", "PCT_VONLY", "PCT_V6", "SEL_FUSED", "SEL_COLS", "SEL_WIN", "SEL_WAVE",
            "SEL_REG", "SELOPS", "RAW_LERPW", "RAW_SEL_TOP", "RAW_SEL_REG", "RO_FUSE", "RO_RUNS", "MULTI_FUSE", "EMIT_HALF", "HIST_WINDOW",
-           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TRACE", "DBG"]
+           "HIST_WS", "HIST_LAYOUT", "APPEND_RESERVE", "REGULAR", "LAST_WALK", "PUT_WALK", "TAGS_SORT", "TRACE", "DBG"]
 
 IDX_C_SHORT4, IDX_C_SHORTV, IDX_C_FAIL = 12, 13, 14                # engine.h: tsdbhip_debug_index slots
 SHARD_AUTO, SHARD_SERIES, SHARD_GROUPS, SHARD_SPANS = -1, 0, 1, 2   # tsdbhip.h TSDB_SHARD_*
@@ -126,6 +127,10 @@ def lib():
         L.tsdbhip_remove.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_int32, vp, C.POINTER(abi.RemoveInfo)]
         L.tsdbhip_last.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp, C.POINTER(abi.LastInfo)]
         L.tsdbhip_put.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.POINTER(abi.PutInfo)]
+        L.tsdbhip_tags_load.argtypes = [vp, C.POINTER(abi.TagTable)]
+        L.tsdbhip_tags_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.tsdbhip_regroup_tags.argtypes = [vp, C.POINTER(abi.TagQuery), C.c_uint32, vp, C.POINTER(abi.TagsInfo)]
+        L.tsdbhip_tags_keys.argtypes = [vp, vp]
         L.tsdbhip_debug_layout.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_loaded.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tsdbhip_synth.argtypes = [vp, C.POINTER(abi.SynthSpec)]
@@ -501,6 +506,46 @@ class Engine:
                                   int(back_scan), ts.ctypes.data, bits.ctypes.data, kind.ctypes.data, C.byref(info)))
         self.last_call_ms = (time.perf_counter() - t0) * 1e3
         return ts[:n_sel], bits[:n_sel], kind[:n_sel], info
+
+    def load_tags(self, tag_ptr, tagk, tagv):
+        """tsdbhip_tags_load: the loaded series' tags in batch order -- tag_ptr[n + 1] from 0, the
+        tagk / tagv UIDs as unsigned integers, tagk strictly ascending inside a series.  The table
+        stays resident until a load or an edit that changes the series numbering drops it."""
+        ptr = np.ascontiguousarray(tag_ptr, dtype=np.int64)
+        k = np.ascontiguousarray(tagk, dtype=np.uint32)
+        v = np.ascontiguousarray(tagv, dtype=np.uint32)
+        if ptr.ndim != 1 or len(ptr) < 1 or k.ndim != 1 or k.shape != v.shape:
+            raise ValueError("tag_ptr needs n + 1 entries, tagk and tagv one entry a tag")
+        if len(k) < int(ptr[-1]):
+            raise ValueError("tag_ptr points past the end of tagk / tagv")
+        t = abi.TagTable(len(ptr) - 1, ptr.ctypes.data, k.ctypes.data if len(k) else None, v.ctypes.data if len(v) else None)
+        _check(lib().tsdbhip_tags_load(self.ctx, C.byref(t)))
+
+    def tags_loaded(self):
+        """tsdbhip_tags_loaded: (series, tags) of the resident tag table, (0, 0) without one."""
+        n, t = C.c_int64(0), C.c_int64(0)
+        _check(lib().tsdbhip_tags_loaded(self.ctx, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def regroup_tags(self, filters, group_by=(), explicit_tags: bool = False, dry: bool = False):
+        """tsdbhip_regroup_tags: the tag filters evaluated, the group keys extracted and numbered in
+        ByteMap order and the batch regrouped, all on the device.  filters: an abi.HostTagQuery, or
+        [(tagk uid, abi.TF_*, ascending tagv uids), ...] with group_by (ascending tagk uids) and
+        explicit_tags.  dry: compute and report only.  Returns (ids int32 in batch order, keys -- the
+        distinct group keys as tuples of tagv uids, in id order --, abi.TagsInfo)."""
+        q = filters if isinstance(filters, abi.HostTagQuery) else abi.HostTagQuery(filters, group_by, explicit_tags)
+        n = C.c_int64(0)
+        # every loaded series, excluded ones included (a context the hook refuses is refused by the call itself)
+        if lib().tsdbhip_debug_loaded(self.ctx, C.byref(n), None) != 0:
+            n = C.c_int64(0)
+        ids = np.zeros(max(1, n.value), np.int32)
+        info = abi.TagsInfo()
+        _check(lib().tsdbhip_regroup_tags(self.ctx, C.byref(q.c), abi.TAGS_DRY if dry else 0, ids.ctypes.data, C.byref(info)))
+        ngb = len(q.group_by_list)
+        kw = np.zeros(max(1, info.n_groups * ngb), np.uint32)
+        _check(lib().tsdbhip_tags_keys(self.ctx, kw.ctypes.data))
+        keys = [tuple(int(x) for x in kw[g * ngb:(g + 1) * ngb]) for g in range(info.n_groups)]
+        return ids[:n.value], keys, info
 
     def load_cells(self, cb: abi.HostCellBatch):
         """tsdbhip_load_cells: the scan's rows compacted on the GPU become the resident batch."""

@@ -190,8 +190,95 @@ class DataPoints:
         return self.metric
 
 
+FILTER_TYPES = ("literal_or", "iliteral_or", "not_literal_or", "not_iliteral_or", "wildcard", "iwildcard", "regexp", "not_key")
+
+
+class TagVFilter:
+    """One 2.x tag value filter (src/query/filter/TagV*Filter.java): its type, tagk, filter string
+    and groupBy flag, with the reference's constructor checks and match(tags) over a
+    {tagk name: tagv name} map."""
+
+    def __init__(self, type: str, tagk: str, filter: str = "", group_by: bool = False):
+        if type not in FILTER_TYPES:
+            raise ValueError(f"Could not find a tag value filter of the type: {type}")
+        if not tagk:
+            raise ValueError("Filter must have a tagk")
+        self.type, self.tagk, self.filter, self.group_by = type, tagk, filter or "", bool(group_by)
+        self.case_insensitive = type in ("iliteral_or", "not_iliteral_or", "iwildcard")
+        f = self.filter
+        if type == "not_key":
+            if f:
+                raise ValueError("The filter must be empty for the not_key filter")
+        elif not f:
+            raise ValueError("Filter cannot be null or empty")
+        if type.endswith("literal_or"):
+            if len(f) == 1 and f == "|":
+                raise ValueError("Filter must contain more than just a pipe")
+            # Java's String.split drops the trailing empty strings
+            parts = f.split("|")
+            while parts and parts[-1] == "":
+                parts.pop()
+            self.literals = {p.lower() if self.case_insensitive else p for p in parts}
+        elif type.endswith("wildcard"):
+            actual = f.lower() if self.case_insensitive else f
+            if "*" not in actual:
+                raise ValueError("Filter must contain an asterisk")
+            self.has_postfix = actual[0] == "*"
+            while actual[0] == "*" and len(actual) >= 2:
+                actual = actual[1:]
+            self.has_prefix = actual[-1] == "*"
+            while actual[-1] == "*" and len(actual) >= 2:
+                actual = actual[:-1]
+            self.components = actual.split("*") if actual.find("*") > 0 else [actual]
+        elif type == "regexp":
+            import re
+            self.pattern = re.compile(f)
+
+    @classmethod
+    def of(cls, entry) -> "TagVFilter":
+        """From a filter list entry: a TagVFilter, or a {"type", "tagk", "filter", "groupBy"} mapping."""
+        if isinstance(entry, cls):
+            return entry
+        return cls(entry["type"], entry["tagk"], entry.get("filter", ""), entry.get("groupBy", False))
+
+    def matches_all(self) -> bool:
+        return self.type.endswith("wildcard") and self.components == ["*"]
+
+    def match_value(self, tagv: str) -> bool:
+        """The filter's verdict on a present tag value (the part of match after the null check)."""
+        if self.type in ("literal_or", "iliteral_or"):
+            return (tagv.lower() if self.case_insensitive else tagv) in self.literals
+        if self.type in ("not_literal_or", "not_iliteral_or"):
+            return (tagv.lower() if self.case_insensitive else tagv) not in self.literals
+        if self.type == "regexp":
+            return self.pattern.search(tagv) is not None
+        if self.type == "not_key":
+            return False
+        if self.matches_all():
+            return True
+        if self.case_insensitive:
+            tagv = tagv.lower()
+        comps = self.components
+        if self.has_postfix and not self.has_prefix and not tagv.endswith(comps[-1]):
+            return False
+        if self.has_prefix and not self.has_postfix and not tagv.startswith(comps[0]):
+            return False
+        idx = 0
+        for c in comps:   # (the reference advances by the component's length, not to the match's end)
+            if tagv.find(c, idx) < 0:
+                return False
+            idx += len(c)
+        return True
+
+    def match(self, tags: dict) -> bool:
+        tagv = tags.get(self.tagk)
+        if tagv is None:   # a missing tag: only the negated filters hold
+            return self.type in ("not_literal_or", "not_iliteral_or", "not_key")
+        return self.match_value(tagv)
+
+
 UNSET = -1
-ROLLUP_USAGES = ("ROLLUP_RAW", "ROLLUP_NOFALLBACK", "ROLLUP_FALLBACK", "ROLLUP_FALLBACK_RAW")
+ROLLUP_USAGES =("ROLLUP_RAW", "ROLLUP_NOFALLBACK", "ROLLUP_FALLBACK", "ROLLUP_FALLBACK_RAW")
 
 
 class TsdbQuery:
@@ -207,6 +294,8 @@ class TsdbQuery:
         self.end_time = UNSET
         self.metric = None
         self.tags = {}
+        self.filters = []                   # setFilters: the 2.x TagVFilter list
+        self.explicit_tags = False
         self.aggregator = None
         self.rate = False
         self.rate_options = RateOptions()
@@ -353,38 +442,84 @@ class TsdbQuery:
             return None
         return best[0]
 
-    def _filters(self):
-        """Tag filters and group-by tag uids of setTimeSeries' tags (None: no series match)."""
+    def setFilters(self, filters, explicit_tags: bool = False):
+        """The 2.x filter list next to the old tags map (TSSubQuery.setFilters / setExplicitTags):
+        TagVFilter objects or {"type", "tagk", "filter", "groupBy"} mappings, ANDed with each other
+        and with setTimeSeries' tags.  explicit_tags: only series with exactly the filtered tag
+        keys match (QueryUtil.getRowKeyUIDRegex without its skip-any-tags parts)."""
+        self.filters = [TagVFilter.of(f) for f in filters]
+        self.explicit_tags = bool(explicit_tags)
+
+    def tag_query(self):
+        """The query's tag filters and group-bys as data for tsdbhip_regroup_tags: an
+        abi.HostTagQuery of filter primitives over UID sets, the group-by tagk uids of
+        findGroupBys (TsdbQuery.java:613-706: a tagk is grouped when any of its filters has
+        groupBy) and explicit_tags; None when no series can match (an unknown tag name, or an
+        unknown literal of the old tags map: NoSuchUniqueName).  The old tags map goes through
+        the same primitives: `*` is ANY plus group-by, `a|b` IN plus group-by, a literal IN.
+        Wildcards, regular expressions and case-insensitive literals are resolved here over the
+        tagv dictionary; every filter but not_key also asks for its tagk to be present, as the row
+        key regex does for every row_key_literals entry (an ANY beside a NOT_IN)."""
         tagk_ids = self.store.tagk.ids
         tagv_ids = self.store.tagv.ids
-        filters = []   # (tagk uid, allowed tagv uid set or None)
-        group_bys = []
+        prims = []   # (tagk uid, abi.TF_*, ascending tagv uids)
+        group_bys = set()
         for k, v in self.tags.items():
             if k not in tagk_ids:
                 return None
             ku = tagk_ids[k]
             if v == "*":
-                group_bys.append(ku)
-                filters.append((ku, None))
+                group_bys.add(ku)
+                prims.append((ku, abi.TF_ANY, []))
             elif "|" in v:
-                allowed = {tagv_ids[x] for x in v.split("|") if x in tagv_ids}
-                group_bys.append(ku)
-                filters.append((ku, allowed))
+                group_bys.add(ku)
+                prims.append((ku, abi.TF_IN, sorted({tagv_ids[x] for x in v.split("|") if x in tagv_ids})))
             else:
                 if v not in tagv_ids:
                     return None
-                filters.append((ku, {tagv_ids[v]}))
-        group_bys.sort()
+                prims.append((ku, abi.TF_IN, [tagv_ids[v]]))
+        for f in self.filters:
+            if f.tagk not in tagk_ids:
+                return None
+            ku = tagk_ids[f.tagk]
+            if f.group_by:
+                group_bys.add(ku)
+            if f.type == "not_key":
+                prims.append((ku, abi.TF_NOT_KEY, []))
+            elif f.matches_all():
+                prims.append((ku, abi.TF_ANY, []))
+            elif f.type in ("not_literal_or", "not_iliteral_or"):
+                prims.append((ku, abi.TF_NOT_IN, sorted(u for name, u in tagv_ids.items() if not f.match_value(name))))
+                prims.append((ku, abi.TF_ANY, []))
+            else:
+                prims.append((ku, abi.TF_IN, sorted(u for name, u in tagv_ids.items() if f.match_value(name))))
+        return abi.HostTagQuery(prims, sorted(group_bys), self.explicit_tags)
+
+    def _filters(self):
+        """Tag filters and group-by tag uids of setTimeSeries' tags and setFilters' list (None: no
+        series match): tag_query()'s primitives as a predicate over a series' (tagk, tagv) uids."""
+        tq = self.tag_query()
+        if tq is None:
+            return None
+        prims = [(ku, kind, set(vs)) for ku, kind, vs in tq.filter_list]
+        wanted = sorted({ku for ku, kind, _ in prims if kind != abi.TF_NOT_KEY}) if tq.explicit_tags else None
 
         def pred(tags):
             d = dict(tags)
-            for ku, allowed in filters:
-                if ku not in d:
+            for ku, kind, vs in prims:
+                has = ku in d
+                if kind == abi.TF_ANY:
+                    ok = has
+                elif kind == abi.TF_IN:
+                    ok = has and d[ku] in vs
+                elif kind == abi.TF_NOT_IN:
+                    ok = not has or d[ku] not in vs
+                else:
+                    ok = not has
+                if not ok:
                     return False
-                if allowed is not None and d[ku] not in allowed:
-                    return False
-            return True
-        return pred, group_bys
+            return wanted is None or sorted(d) == wanted
+        return pred, list(tq.group_by_list)
 
     @staticmethod
     def _groups(spans, group_bys):
@@ -426,48 +561,12 @@ class TsdbQuery:
         """findSpans + GroupByAndAggregateCB grouping (TsdbQuery.java:795-1049).
         Returns (HostBatch, group keys in emission order)."""
         s, e = self.scan_bounds()
-        tagk_ids = self.store.tagk.ids
-        tagv_ids = self.store.tagv.ids
-        filters = []   # (tagk uid, allowed tagv uid set or None)
-        group_bys = []
-        for k, v in self.tags.items():
-            if k not in tagk_ids:
-                return make_batch([], []), []
-            ku = tagk_ids[k]
-            if v == "*":
-                group_bys.append(ku)
-                filters.append((ku, None))
-            elif "|" in v:
-                allowed = {tagv_ids[x] for x in v.split("|") if x in tagv_ids}
-                group_bys.append(ku)
-                filters.append((ku, allowed))
-            else:
-                if v not in tagv_ids:
-                    return make_batch([], []), []
-                filters.append((ku, {tagv_ids[v]}))
-        group_bys.sort()
-
-        def pred(tags):
-            d = dict(tags)
-            for ku, allowed in filters:
-                if ku not in d:
-                    return False
-                if allowed is not None and d[ku] not in allowed:
-                    return False
-            return True
-
+        f = self._filters()
+        if f is None:   # an unknown tag name or literal value: no series matches
+            return make_batch([], []), []
+        pred, group_bys = f
         spans = self._data_store().scan(self.metric, s, e, pred)
-        if not group_bys:
-            keys = [()]
-            gids = [0] * len(spans)
-        else:
-            key_of = []
-            for sk, _ in spans:
-                d = dict(sk[1])
-                key_of.append(tuple(d.get(ku, -1) for ku in group_bys))
-            keys = sorted({k for k in key_of if -1 not in k})  # ByteMap order of the uid bytes
-            index = {k: i for i, k in enumerate(keys)}
-            gids = [index.get(k, -1) for k in key_of]
+        keys, gids = self._groups(spans, group_bys)
         return make_batch(spans, gids), keys
 
     def _best_rollups(self):
@@ -585,9 +684,12 @@ class ResidentSpans:
     run(tsdb_query) answers a raw-table TsdbQuery over `store` whose scan range lies inside the
     resident one: the query's tag filters decide which resident spans are visible
     (abi.GROUP_EXCLUDED for the others) and its group-by tags number the visible ones, with the
-    query's own _filters() / _groups() logic."""
+    query's own _filters() / _groups() logic.  With device_tags the spans' tags are resident too
+    (Engine.load_tags) and run() leaves filtering, key extraction and numbering to the device
+    (Engine.regroup_tags, tsdbhip_regroup_tags) instead of walking every span's tags here."""
 
-    def __init__(self, store: MockStore, metric: str, scan_start_s: int, scan_end_s: int, engine=None):
+    def __init__(self, store: MockStore, metric: str, scan_start_s: int, scan_end_s: int, engine=None,
+                 device_tags: bool = False):
         if scan_end_s <= scan_start_s:
             raise ValueError("empty resident scan range")
         self.store = store
@@ -602,6 +704,14 @@ class ResidentSpans:
         self.span_keys = [sk for sk, _ in self.spans]
         # (loaded ungrouped: every run() regroups before it queries)
         self.engine.load(make_batch(self.spans, [abi.GROUP_NONE] * len(self.spans)))
+        self.device_tags = bool(device_tags)
+        if self.device_tags:
+            self._load_tags()
+
+    def _load_tags(self):
+        """The resident tag table of span_keys (Engine.load_tags, tsdbhip_tags_load): at construction,
+        and again after an edit that added or retired a series -- the engine drops its table then."""
+        self.engine.load_tags(*abi.tag_table_arrays([sk[1] for sk in self.span_keys]))
 
     def group_ids(self, query: TsdbQuery):
         """(group id of every resident span for `query`, group keys in emission order)."""
@@ -651,6 +761,8 @@ class ResidentSpans:
         self.spans = spans
         self.span_keys = merged_keys
         self.scan_end_s = scan_end_s
+        if self.device_tags and any(series_new):
+            self._load_tags()
         return info
 
     def refresh(self, from_s: int, to_s: int | None = None, remove_missing: bool = False):
@@ -698,6 +810,8 @@ class ResidentSpans:
             spans.append((sk, [by_base[b] for b in sorted(by_base)]))
         self.spans = spans
         self.span_keys = merged_keys
+        if self.device_tags and any(series_new):
+            self._load_tags()
         return info
 
     def put(self, points):
@@ -804,6 +918,8 @@ class ResidentSpans:
             raise RuntimeError("the engine retired other series than the row-less spans")
         self.spans = kept
         self.span_keys = [sk for sk, _ in kept]
+        if self.device_tags and any(x < 0 for x in new_index):
+            self._load_tags()
 
     @staticmethod
     def tsuid_of(series_key) -> str:
@@ -869,10 +985,20 @@ class ResidentSpans:
         if s < self.scan_start_s or e > self.scan_end_s:
             raise ValueError(f"the query scans [{s}, {e}), outside the resident range "
                              f"[{self.scan_start_s}, {self.scan_end_s})")
-        ids, keys = self.group_ids(query)
-        if not self.spans:
-            return []
-        self.engine.regroup(ids)
+        if self.device_tags:
+            if not self.spans:
+                return []
+            tq = query.tag_query()
+            if tq is None:   # an unknown tag name or literal value: no series matches
+                keys = []
+                self.engine.regroup([abi.GROUP_EXCLUDED] * len(self.spans))
+            else:
+                _, keys, _ = self.engine.regroup_tags(tq)
+        else:
+            ids, keys = self.group_ids(query)
+            if not self.spans:
+                return []
+            self.engine.regroup(ids)
         out = []
         for gid, ts, bits, isi in self.engine.run(query.to_abi()):
             key = keys[gid] if (query.aggregator != "none" and 0 <= gid < len(keys)) else ()
