@@ -1193,6 +1193,14 @@ int tsdbhip_debug_rollup(tsdbhip_ctx* ctx, int64_t out[4]);
  * answers TSDB_E_NOT_IMPLEMENTED. */
 int tsdbhip_debug_pct(tsdbhip_ctx* ctx, int64_t out[6]);
 
+/* Test hook (no reference counterpart): the device and page-locked host buffers the library holds
+ * in this process, over every context -- live allocations and the bytes allocated for them, device
+ * memory then page-locked memory.  tsdbhip_destroy returns all four to what they were before the
+ * context's tsdbhip_init.  (The pinned result blocks and tsdbhip_host_alloc are not counted, nor
+ * is the temporary storage of the scans and sorts.)  Takes no context and no lock; relaxed
+ * atomic reads.  Any pointer may be null. */
+int tsdbhip_debug_buffers(int64_t* dev_n, uint64_t* dev_bytes, int64_t* host_n, uint64_t* host_bytes);
+
 #ifdef __cplusplus
 }
 #endif

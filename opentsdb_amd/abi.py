@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 from collections.abc import Sequence
+from typing import NamedTuple
 
 import numpy as np
 
@@ -415,6 +416,14 @@ class TagsInfo(C.Structure):
         ("table_bytes", C.c_int64),
         ("kernel_ms", C.c_double),
     ]
+
+
+class BufferCounts(NamedTuple):
+    """tsdbhip_debug_buffers: the library's live device and page-locked host buffers, process-wide."""
+    dev_n: int
+    dev_bytes: int
+    host_n: int
+    host_bytes: int
 
 
 class HostTagQuery:

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/tsdbhip.h"
+#include "devbuf.h"
 #include "engine.h"
 #include "multi.h"
 #include "ksel.h"
@@ -326,47 +327,6 @@ bool jcal_prev(const JZone& Z, int64_t ts, int64_t n, int unit, int64_t& out) {
 // k_fast's vle class loads a 1 KB value window from each row start
 constexpr int64_t BLOB_SLACK = 1024 + 64;
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e == hipSuccess) n = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// page-locked host staging (device -> host copies of dense results), grown on demand
-struct HostBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= n && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault);
-    if (e == hipSuccess) n = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
-
 }  // namespace
 
 // One RollupSeq of a rollup batch (RollupSpan.addRow merges the cells of one row key):
@@ -409,8 +369,7 @@ struct tsdbhip_ctx {
   DevBuf rg_ent;                       // [n_series_loaded] RegroupParams.ent
   HostBuf rg_stage;                    // ... page-locked
   HostBuf rg_rows;                     // the gathered descriptors, downloaded for the host mirrors
-  void* rg_tmp = nullptr;              // the scan's temporary storage
-  size_t rg_tmp_bytes = 0;
+  DevBuf rg_tmp;                       // the scan's temporary storage
   std::vector<uint8_t> h_excl;         // [batch index] excluded by the last regroup (empty: none)
   // tsdbhip_append: the blobs are capacity-managed (qual.n / val.n >= qual_bytes / val_bytes +
   // BLOB_SLACK, val2.n == qual.n when present); bytes of replaced rows stay where they are
@@ -534,7 +493,7 @@ struct tsdbhip_ctx {
   void* small_dst[16] = {};
   int small_len[16] = {};
   int small_n = 0;
-  void* up_stage[2] = {nullptr, nullptr};   // h2d: page-locked staging of pageable uploads (UP_CHUNK each)
+  HostBuf up_stage[2];                      // h2d: page-locked staging of pageable uploads (UP_CHUNK each)
   hipEvent_t up_ev[2] = {nullptr, nullptr};
   bool up_busy[2] = {false, false};
   const int32_t* redo_final = nullptr;   // device counter of the tiles k_fast handed to k_grid
@@ -557,8 +516,7 @@ struct tsdbhip_ctx {
   // rollup generation: scratch and the per-function cells of the last tsdbhip_rollup_run
   DevBuf ro_allint, ro_ord, ro_orig, ro_cnt, ro_vsz, ro_coff, ro_voff;
   DevBuf ro_agg, ro_pres;              // fused rollup pass: [4][series][K] values, [series][K] presence
-  void* ro_tmp = nullptr;
-  size_t ro_tmp_bytes = 0;
+  DevBuf ro_tmp;
   struct RollupOut {
     DevBuf series, base, qual, voff, val;
     int64_t cells = 0;
@@ -571,8 +529,7 @@ struct tsdbhip_ctx {
   struct Preagg {
     DevBuf val, flag, act, qerr, code, off, totals;   // slab [F][G][K], [F][G], [F]; [n + 1] codes / offsets
     DevBuf o_func, o_group, o_base, o_qual, o_voff, o_val;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    DevBuf tmp;
     hipEvent_t ev[3] = {};
     int64_t cells = 0;
     uint64_t qual_bytes = 0, value_bytes = 0;
@@ -598,8 +555,7 @@ struct tsdbhip_ctx {
   // query's scan range covers them (SaltScanner.processRow fails the scan)
   struct CmpErr { int64_t series, row; int64_t base; int32_t code; };
   std::vector<CmpErr> cmp_errs;
-  void* cmp_tmp = nullptr;
-  size_t cmp_tmp_bytes = 0;
+  DevBuf cmp_tmp;
   bool ro_scan_valid = false;          // scan-active value series of the last scan range
   // the last scan range whose rollup rows passed ro_scan's checks (a host walk over every row:
   // 4 ms a query for a 1M-series table; the store is immutable until the next load)
@@ -899,6 +855,7 @@ static void invalidate_derived(tsdbhip_ctx* c) {
 
 // The resident tag table goes with the series numbering it was loaded for: every load, and an edit
 // that adds or retires a series.  A context that never loaded one has nothing to release.
+// (Like release_batch's, this list is release policy, not ownership.)
 static void drop_tags(tsdbhip_ctx* c) {
   if (!c->tg_loaded && !c->tg_have_keys) return;
   for (DevBuf* b : {&c->tg_ptr, &c->tg_pairs, &c->tg_q, &c->tg_ids, &c->tg_kw, &c->tg_s[0], &c->tg_s[1], &c->tg_s[2], &c->tg_s[3],
@@ -911,6 +868,9 @@ static void drop_tags(tsdbhip_ctx* c) {
   c->tg_n_gb = 0;
 }
 
+// What a load hands back to the device.  The list is policy, not ownership: every buffer frees
+// itself with the context (devbuf.h), and a null .p carries meaning here -- val2.p tells whether the
+// batch has an int16 copy.  A buffer missing from the list keeps its capacity until tsdbhip_destroy.
 static void release_batch(tsdbhip_ctx* c) {
   drop_tags(c);
   for (DevBuf* b : {&c->rows, &c->srp, &c->qual, &c->val, &c->val2, &c->hint, &c->ilist, &c->icnt, &c->gid, &c->d_tb, &c->d_te, &c->d_tg, &c->d_gtp,
@@ -967,47 +927,17 @@ extern "C" void tsdbhip_destroy(tsdbhip_ctx* c) {
   if (!c) return;
   if (c->md) { tsdb::md_destroy(c->md); c->md = nullptr; }
   (void)hipSetDevice(c->device);
+  // nothing is freed under work in flight; the buffers then free themselves with the context,
+  // while its device is current
   (void)hipStreamSynchronize(c->stream);
-  release_batch(c);
-  for (DevBuf* b : {&c->pa, &c->pb, &c->pn, &c->pf, &c->out_val, &c->out_flag, &c->gact, &c->err, &c->g_dense,
-                    &c->g_pres, &c->g_rate, &c->redo, &c->redo_n, &c->redo2, &c->redo2_n, &c->d_tl, &c->d_tl_n, &c->r1a, &c->r1b, &c->r3a, &c->r3b, &c->r2, &c->r_n, &c->xbuf, &c->gbuf, &c->r_rowpt,
-                    &c->r_spoff, &c->r_spn, &c->r_grp, &c->r_pts, &c->r_rank, &c->r_bm, &c->r_wb, &c->r_U, &c->r_ooff,
-                    &c->r_sg, &c->r_su, &c->r_ots, &c->r_obits, &c->r_oint, &c->r_coff, &c->r_cur, &c->r_voff, &c->r_vl, &c->r_vd, &c->r_vp, &c->pre_dense, &c->pre_pres,
-                    &c->row_ser, &c->sr_list, &c->sr_n, &c->sr_mark,
-                    &c->ro_allint, &c->ro_ord, &c->ro_orig, &c->ro_cnt, &c->ro_vsz, &c->ro_coff, &c->ro_voff,
-                    &c->big_scratch, &c->ro_agg, &c->ro_pres})
-    b->release();
-  c->h_stage.release();
-  c->h_small.release();
-  c->h_scal.release();
-  for (auto& o : c->ro_out)
-    for (DevBuf* b : {&o.series, &o.base, &o.qual, &o.voff, &o.val}) b->release();
-  if (c->ro_tmp) (void)hipFree(c->ro_tmp);
-  for (DevBuf* b : {&c->pg.val, &c->pg.flag, &c->pg.act, &c->pg.qerr, &c->pg.code, &c->pg.off, &c->pg.totals,
-                    &c->pg.o_func, &c->pg.o_group, &c->pg.o_base, &c->pg.o_qual, &c->pg.o_voff, &c->pg.o_val})
-    b->release();
-  if (c->pg.tmp) (void)hipFree(c->pg.tmp);
-  for (auto& e : c->pg.ev) if (e) (void)hipEventDestroy(e);
-  if (c->cmp_tmp) (void)hipFree(c->cmp_tmp);
-  if (c->rg_tmp) (void)hipFree(c->rg_tmp);
-  c->rg_stage.release();
-  c->rg_rows.release();
-  c->ap_stage.release();
-  c->rm_stage.release();
-  c->ls_stage.release();
-  c->pt_stage.release();
+  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   tsdb::hist_release(c->hist);
   c->hist = nullptr;
-  for (DevBuf* b : {&c->sel_vals, &c->sel_sorted, &c->sel_uni, &c->sel_gsp, &c->cal_bounds, &c->sel_wr, &c->first_ts,
-                    &c->hw_mark, &c->m_sum, &c->m_mn, &c->m_mx, &c->m_mean, &c->m_m2, &c->m_nl, &c->m_nz, &c->m_f})
-    b->release();
-  for (int i = 0; i < 2; i++) {
-    if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]);
-    if (c->up_stage[i]) (void)hipHostFree(c->up_stage[i]);
-  }
+  for (auto& e : c->pg.ev) if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->up_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->cev) if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
+  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1892,18 +1822,17 @@ extern "C" int tsdbhip_load_rollup(tsdbhip_ctx* c, const tsdbhip_rollup_batch* r
     }
     c->ro_npairs = (int64_t)vrows.size();
     if (c->ro_npairs && c->n_rows < ((int64_t)1 << 31)) {
-      DevBuf dv, ds;
-      HIP_OK(dv.ensure(c->ro_npairs * 4));
-      HIP_OK(ds.ensure(c->ro_npairs * 4));
-      HIP_OK(hipMemcpy(dv.p, vrows.data(), c->ro_npairs * 4, hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(ds.p, vser.data(), c->ro_npairs * 4, hipMemcpyHostToDevice));
-      HIP_OK(c->ro_pairs.ensure(c->ro_npairs * (int64_t)sizeof(RoPair)));
-      HIP_OK(launch_ro_pack(c->rows.as<RowDesc>(), cnt ? c->ro_partner.as<int32_t>() : nullptr, dv.as<int32_t>(),
-                            ds.as<int32_t>(), c->qual.as<uint8_t>(), c->ro_npairs, c->ro_pairs.as<RoPair>(), c->stream));
-      const hipError_t e = hipStreamSynchronize(c->stream);
-      dv.release();   // (DevBuf frees nothing on its own)
-      ds.release();
-      HIP_OK(e);
+      {
+        DevBuf dv, ds;
+        HIP_OK(dv.ensure(c->ro_npairs * 4));
+        HIP_OK(ds.ensure(c->ro_npairs * 4));
+        HIP_OK(hipMemcpy(dv.p, vrows.data(), c->ro_npairs * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(ds.p, vser.data(), c->ro_npairs * 4, hipMemcpyHostToDevice));
+        HIP_OK(c->ro_pairs.ensure(c->ro_npairs * (int64_t)sizeof(RoPair)));
+        HIP_OK(launch_ro_pack(c->rows.as<RowDesc>(), cnt ? c->ro_partner.as<int32_t>() : nullptr, dv.as<int32_t>(),
+                              ds.as<int32_t>(), c->qual.as<uint8_t>(), c->ro_npairs, c->ro_pairs.as<RoPair>(), c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+      }
       int rc = ro_build_runs(c);
       if (rc) return rc;
     } else {
@@ -1981,17 +1910,10 @@ extern "C" int tsdbhip_load_cells(tsdbhip_ctx* c, const tsdbhip_cell_batch* cb) 
   CtxLock lk(c);
   HIP_OK(hipSetDevice(c->device));
   release_batch(c);
-  // device copies of one chunk of the scan and per-column / per-row scratch (freed at the end)
+  // device copies of one chunk of the scan and per-column / per-row scratch (they go with the call)
   DevBuf d_rcp, d_cqo, d_cvo, d_cts, d_q, d_v, d_crow, d_cn, d_coff, d_cinfo, d_rheap, d_rone, d_rerr;
   DevBuf d_key, d_key2, d_idx, d_idx2, d_ecol, d_eqo, d_evo, d_klen, d_sq, d_sv, d_sc, d_sm;
   DevBuf d_rlo, d_rq, d_rv, d_rstate, d_rmeta, d_rdq, d_rdv, d_raw, d_bad, d_rmax, d_klist, d_cq32, d_cv32;
-  auto release_all = [&]() {
-    for (DevBuf* b : {&d_rcp, &d_cqo, &d_cvo, &d_cts, &d_q, &d_v, &d_crow, &d_cn, &d_coff, &d_cinfo, &d_rheap, &d_rone,
-                      &d_rerr, &d_key, &d_key2, &d_idx, &d_idx2, &d_ecol, &d_eqo, &d_evo, &d_klen, &d_sq, &d_sv,
-                      &d_sc, &d_sm, &d_rlo, &d_rq, &d_rv, &d_rstate, &d_rmeta, &d_rdq, &d_rdv, &d_raw, &d_bad, &d_rmax, &d_klist, &d_cq32, &d_cv32})
-      b->release();
-  };
-  struct Rel { std::function<void()> f; ~Rel() { f(); } } rel{release_all};
   const hipStream_t st = c->stream;
   const int64_t R1 = std::max<int64_t>(1, NR);
   std::vector<int64_t> rq(R1), rv(R1), rdq(R1, -1), rdv(R1, -1);
@@ -2068,7 +1990,7 @@ extern "C" int tsdbhip_load_cells(tsdbhip_ctx* c, const tsdbhip_cell_batch* cb) 
     p.row_one = d_rone.as<int64_t>();
     p.row_err = d_rerr.as<int32_t>();
     HIP_OK(hipEventRecord(c->ev[0], st));
-    HIP_OK(cmp_analyze(p, &c->cmp_tmp, &c->cmp_tmp_bytes, st));
+    HIP_OK(cmp_analyze(p, &c->cmp_tmp.p, &c->cmp_tmp.n, st));
     int64_t n_ent = 0;
     { int rc_ = d2h_small(c, &n_ent, p.col_off + nc, 8, st); if (rc_) return rc_; }
     { int rc_ = sync_small(c, st); if (rc_) return rc_; }
@@ -2120,7 +2042,7 @@ extern "C" int tsdbhip_load_cells(tsdbhip_ctx* c, const tsdbhip_cell_batch* cb) 
     p.row_lo = d_rlo.as<int64_t>();
     int rb = 1;
     while (((int64_t)1 << rb) <= nr) rb++;
-    HIP_OK(cmp_entries(p, &c->cmp_tmp, &c->cmp_tmp_bytes, std::min(64, 22 + rb), st));
+    HIP_OK(cmp_entries(p, &c->cmp_tmp.p, &c->cmp_tmp.n, std::min(64, 22 + rb), st));
     }
     HIP_OK(hipEventRecord(c->ev[2], st));
     if (nr) {
@@ -2665,15 +2587,14 @@ extern "C" int tsdbhip_synth_shard(tsdbhip_ctx* c, const tsdbhip_synth_spec* sp,
 }
 
 // ===========================================================================
-// in-place edits of the resident batch: tsdbhip_regroup, tsdbhip_append, tsdbhip_upsert,
-// tsdbhip_trim, tsdbhip_remove.  One skeleton: validate, allocate, queue, download, commit,
+// in-place edits of the resident batch: tsdbhip_regroup, tsdbhip_regroup_tags, tsdbhip_append,
+// tsdbhip_upsert, tsdbhip_put, tsdbhip_trim, tsdbhip_remove.  One skeleton: validate, allocate, queue, download, commit,
 // invalidate_derived, finish_classes -- the resident batch stays as it is until the commit.
 // ===========================================================================
 
 // blobs an edit allocated and has not handed to the context
 struct BlobHold {
   DevBuf q, v, v2;
-  ~BlobHold() { q.release(); v.release(); v2.release(); }
 };
 
 // an edit's blob allocation failed; hint: what did not fit
@@ -2951,7 +2872,7 @@ static int regroup_apply(tsdbhip_ctx* c, const int32_t* group_id, int32_t maxg) 
   HIP_OK(c->reg2.ensure(std::max<size_t>(1, (size_t)NR) * sizeof(RegRow)));
   rp.reg_old = c->reg.as<RegRow>();
   rp.reg_new = c->reg2.as<RegRow>();
-  HIP_OK(regroup_scan(rp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(regroup_scan(rp, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
   HIP_OK(launch_regroup(rp, c->stream));
   // host mirrors in the new order: series_row_ptr from the old one while the device works
   Mirrors m;
@@ -3000,7 +2921,6 @@ extern "C" int tsdbhip_tags_load(tsdbhip_ctx* c, const tsdbhip_tag_table* t) {
   HIP_OK(hipSetDevice(c->device));
   // the new table beside the old one, which stays until both copies are over
   DevBuf ptr, pairs;
-  struct Hold { DevBuf &a, &b; ~Hold() { a.release(); b.release(); } } hold{ptr, pairs};
   HIP_OK(ptr.ensure((size_t)(N + 1) * 8));
   HIP_OK(pairs.ensure(std::max<size_t>(1, (size_t)T) * sizeof(uint2)));
   std::vector<uint2> hp((size_t)T);
@@ -3164,8 +3084,8 @@ extern "C" int tsdbhip_regroup_tags(tsdbhip_ctx* c, const tsdbhip_tag_query* q, 
     HIP_OK(hipMemsetAsync(p.cpres, 0, (size_t)(TAGS_RANK_MAX_KEYS + 1) * 4, c->stream));
   }
   HIP_OK(launch_tags_match(p, c->stream));
-  if (route == TAGS_ROUTE_RANK) HIP_OK(tags_number_rank(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
-  if (route == TAGS_ROUTE_SORT) HIP_OK(tags_number_sort(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  if (route == TAGS_ROUTE_RANK) HIP_OK(tags_number_rank(p, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
+  if (route == TAGS_ROUTE_SORT) HIP_OK(tags_number_sort(p, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
   HIP_OK(download());   // the one synchronisation
   if (route == TAGS_ROUTE_RANK && !hm->rank_ok) {
     // more composite keys than the rank route's map holds: the verdicts and the key words stand, the
@@ -3173,7 +3093,7 @@ extern "C" int tsdbhip_regroup_tags(tsdbhip_ctx* c, const tsdbhip_tag_query* q, 
     route = TAGS_ROUTE_SORT;
     HIP_OK(ensure_route(route));
     fill(route);
-    HIP_OK(tags_number_sort(p, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(tags_number_sort(p, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
     HIP_OK(download());
   }
   float ms = 0;
@@ -3501,7 +3421,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     rp.hit = c->up_hit.as<int32_t>();
     HIP_OK(launch_upsert_rank(rp, c->stream));
     HIP_OK(tr.mark(6));
-    HIP_OK(upsert_scan_hits(rp.hit, c->up_S.as<int32_t>(), DR, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(upsert_scan_hits(rp.hit, c->up_S.as<int32_t>(), DR, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
     HIP_OK(tr.mark(7));
     h_lb.resize(DR);
     h_hit.resize(DR);
@@ -3553,7 +3473,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
   uint32_t sus_cnt[16] = {};
   float t_sus = 0;
   if (!upsert) {
-    HIP_OK(append_scan(ap, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(append_scan(ap, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
     HIP_OK(launch_append(ap, c->stream));
     HIP_OK(launch_append_recede(ap, c->ap_touch.as<int32_t>(), n_touched, qp, c->stream));
   } else {
@@ -3603,7 +3523,7 @@ static int merge_delta(tsdbhip_ctx* c, const tsdbhip_batch* delta, const int64_t
     up.reg_delta = dreg;
     up.reg_new = ap.reg_new;
     HIP_OK(tr.mark(8));
-    HIP_OK(upsert_scan(up, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+    HIP_OK(upsert_scan(up, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
     HIP_OK(launch_upsert(up, c->stream));
     HIP_OK(tr.mark(9));
     if (n_sus) {   // indexed again before the walk (the delta's pass is through with hint / ilist)
@@ -4001,7 +3921,7 @@ struct BlobPack {
   }
   int queue(tsdbhip_ctx* c, RowDesc* rows_new, int64_t nr2) {
     if (!on) return 0;
-    HIP_OK(trim_pack_scan(rows_new, nr2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp, &c->rg_tmp_bytes,
+    HIP_OK(trim_pack_scan(rows_new, nr2, c->tr_qdst.as<uint64_t>(), c->tr_vdst.as<uint64_t>(), &c->rg_tmp.p, &c->rg_tmp.n,
                           c->stream));
     // (the slack past the packed end, and the reserve, read as zeros)
     HIP_OK(hipMemsetAsync(hold.q.as<uint8_t>() + live_q, 0, hold.q.n - live_q, c->stream));
@@ -4132,7 +4052,6 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   // first indexed, so the pass rewrites the same bytes; a copy allocated only because the pass
   // wants one goes with `idx_v2`.
   DevBuf idx_v2;
-  struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_idx_v2{idx_v2};
   IndexPlan ip;
   ip.fn = &fn;
   ip.nomem_hint = nomem_hint;
@@ -4162,7 +4081,7 @@ extern "C" int tsdbhip_trim(tsdbhip_ctx* c, int64_t cutoff_s, int32_t pack_dead_
   tp.srp_new = c->srp2.as<int64_t>();
   tp.rows_new = c->rows2.as<RowDesc>();
   tp.reg_new = c->reg2.as<RegRow>();
-  HIP_OK(trim_scan(tp, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(trim_scan(tp, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
   HIP_OK(launch_trim_gather(tp, c->stream));
   HIP_OK(tr.mark(1));
   uint32_t idx_cnt[16] = {};
@@ -4456,7 +4375,6 @@ extern "C" int tsdbhip_remove(tsdbhip_ctx* c, const tsdbhip_remove_range* ranges
   if (dropped) HIP_OK(c->gid2.ensure(std::max<size_t>(1, (size_t)N2) * 4));
   HIP_OK(c->rg_rows.ensure(std::max<size_t>(1, (size_t)NR2) * sizeof(RowDesc)));
   DevBuf idx_v2;   // (an int16 copy allocated only because the suspects' pass wants one goes with the call)
-  struct Drop { DevBuf& b; ~Drop() { b.release(); } } drop_idx_v2{idx_v2};
   IndexPlan ip;
   ip.fn = &fn;
   ip.nomem_hint = nomem_hint;
@@ -4474,7 +4392,7 @@ extern "C" int tsdbhip_remove(tsdbhip_ctx* c, const tsdbhip_remove_range* ranges
   // ---- queued work: the scans, the gather, the suspects' index and walk, the pack ----
   HIP_OK(hipMemcpyAsync(c->srp2.p, st_n_srp, (size_t)(N2 + 1) * 8, hipMemcpyHostToDevice, c->stream));
   if (dropped && N2) HIP_OK(hipMemcpyAsync(c->gid2.p, st_key, (size_t)N2 * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(remove_scan(c->rm_diff.as<int32_t>(), c->rm_pos.as<int32_t>(), NR, &c->rg_tmp, &c->rg_tmp_bytes, c->stream));
+  HIP_OK(remove_scan(c->rm_diff.as<int32_t>(), c->rm_pos.as<int32_t>(), NR, &c->rg_tmp.p, &c->rg_tmp.n, c->stream));
   HIP_OK(tr.mark(2));
   RemoveParams rp{};
   rp.pos = c->rm_pos.as<int32_t>();
@@ -4764,6 +4682,14 @@ extern "C" int tsdbhip_debug_sel_window(tsdbhip_ctx* c, int64_t* runs, int64_t* 
 
 // Test hook: the route of the last tsdbhip_rollup_run (streaming pass launched, its series, class
 // A's hand-backs, the series k_rollup_agg reduced).
+extern "C" int tsdbhip_debug_buffers(int64_t* dev_n, uint64_t* dev_bytes, int64_t* host_n, uint64_t* host_bytes) {
+  if (dev_n) *dev_n = dev_live.n.load(std::memory_order_relaxed);
+  if (dev_bytes) *dev_bytes = dev_live.bytes.load(std::memory_order_relaxed);
+  if (host_n) *host_n = host_live.n.load(std::memory_order_relaxed);
+  if (host_bytes) *host_bytes = host_live.bytes.load(std::memory_order_relaxed);
+  return 0;
+}
+
 extern "C" int tsdbhip_debug_rollup(tsdbhip_ctx* c, int64_t out[4]) {
   MD_REFUSE(c, "tsdbhip_debug_rollup");
   if (!c) return fail(TSDB_E_ILLEGAL_ARGUMENT, "null ctx");
@@ -8684,8 +8610,8 @@ extern "C" int tsdbhip_rollup_run(tsdbhip_ctx* c, const tsdbhip_rollup_spec* sp,
     rp.err = c->err.as<int32_t>();
     HIP_OK(launch_rollup_size(rp, c->stream));
     if (NK > 0x7FFFFFFFLL) return fail(TSDB_E_NOT_IMPLEMENTED, "more than 2^31 rollup buckets in one pass");
-    if (NK) HIP_OK(rollup_scan(rp.cnt, c->ro_coff.as<int64_t>(), rp.vsz, c->ro_voff.as<uint64_t>(), NK, &c->ro_tmp,
-                               &c->ro_tmp_bytes, c->stream));
+    if (NK) HIP_OK(rollup_scan(rp.cnt, c->ro_coff.as<int64_t>(), rp.vsz, c->ro_voff.as<uint64_t>(), NK, &c->ro_tmp.p,
+                               &c->ro_tmp.n, c->stream));
     // totals = last offset + last element
     int64_t last_off = 0;
     uint64_t last_voff = 0;
@@ -8910,7 +8836,7 @@ extern "C" int tsdbhip_preagg_run(tsdbhip_ctx* c, const tsdbhip_preagg_spec* sp,
   pp.err = c->err.as<int32_t>();
   pp.totals = pg.totals.as<PreaggTotals>();
   HIP_OK(launch_preagg_size(pp, c->stream));
-  HIP_OK(preagg_scan(pp.code, pg.off.as<uint64_t>(), n + 1, &pg.tmp, &pg.tmp_bytes, c->stream));
+  HIP_OK(preagg_scan(pp.code, pg.off.as<uint64_t>(), n + 1, &pg.tmp.p, &pg.tmp.n, c->stream));
   HIP_OK(launch_preagg_write(pp, c->stream));
   HIP_OK(hipEventRecord(pg.ev[2], c->stream));
   HIP_OK(c->h_small.ensure(sizeof(PreaggTotals)));
@@ -8991,9 +8917,9 @@ hipError_t h2d(tsdbhip_ctx* c, void* dst, const void* src, size_t n, hipStream_t
   }
   (void)hipGetLastError();   // (pageable memory: no attributes)
   for (int i = 0; i < 2; i++) {
-    if (!c->up_stage[i]) {
-      hipError_t e = hipHostMalloc(&c->up_stage[i], UP_CHUNK, hipHostMallocDefault);
-      if (e != hipSuccess) { c->up_stage[i] = nullptr; return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st); }
+    if (!c->up_stage[i].p) {
+      hipError_t e = c->up_stage[i].ensure(UP_CHUNK);
+      if (e != hipSuccess) return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st);
       e = hipEventCreateWithFlags(&c->up_ev[i], hipEventDisableTiming);
       if (e != hipSuccess) return e;
     }
@@ -9008,7 +8934,7 @@ hipError_t h2d(tsdbhip_ctx* c, void* dst, const void* src, size_t n, hipStream_t
       const hipError_t e = hipEventSynchronize(c->up_ev[b]);
       if (e != hipSuccess) return e;
     }
-    char* stage = static_cast<char*>(c->up_stage[b]);
+    char* stage = static_cast<char*>(c->up_stage[b].p);
     const int nt = len >= ((size_t)8 << 20) ? pool.width() : 1;
     const std::function<void(int)> part = [&](int t) {
       const size_t a0 = (len * t / nt) & ~(size_t)63, a1 = t + 1 == nt ? len : (len * (t + 1) / nt) & ~(size_t)63;

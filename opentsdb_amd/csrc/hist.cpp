@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/tsdbhip.h"
+#include "devbuf.h"
 #include "hist.h"
 
 namespace tsdb {
@@ -41,35 +42,15 @@ namespace {
     if (_e != hipSuccess) return set_error(TSDB_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-struct Buf {
-  void* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e == hipSuccess) n = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 // The resident histogram store.
 struct HistStore {
   bool loaded = false;
   int64_t n_series = 0, n_cells = 0, n_pos = 0;
-  Buf val, voff, codec, status, hkey, hcount, hidx, dlo, dup, lkey, lidx, lkey2, lidx2;
+  DevBuf val, voff, codec, status, hkey, hcount, hidx, dlo, dup, lkey, lidx, lkey2, lidx2;
   int lslots = 64;                              // k_hist_accw's compact LDS dictionary table
   bool lds_dict = false;                        // the dictionary fits the LDS table of k_hist_accum
-  Buf pos_cell, pos_ts, pos_kind, row_pos;
-  Buf col_lid, lay_col, lay_off, lay_di;        // bucket layouts: dictionary indices without the keys
+  DevBuf pos_cell, pos_ts, pos_kind, row_pos;
+  DevBuf col_lid, lay_col, lay_off, lay_di;        // bucket layouts: dictionary indices without the keys
   int64_t n_layouts = 0;
   int32_t D = 0;
   int64_t max_ts = 0;                           // largest datapoint timestamp of the store (ms)
@@ -79,23 +60,21 @@ struct HistStore {
   std::vector<uint32_t> row_base;               // [kept rows]
   std::vector<int32_t> group;                   // [n_series]
   // query scratch
-  Buf q_rlo, q_rhi, q_out, q_slot, q_key, q_key2, q_pos, q_pos2, q_head, q_incl, q_point, q_ptts, q_ptgrp;
-  Buf q_vlen, q_voff, q_vpos, q_tix;   // windowed accumulation: the spans' positions in output-group order, their entries
-  Buf q_caltab, q_spcal;         // calendar downsampling: boundary runs per span anchor
-  Buf q_gsp, q_spq, q_spts;      // greedy walk over spans out of time order (k_hist_walk)
-  Buf acc, pres, pkind, flag, ptout, err, pct;
-  Buf o_ts, o_grp, o_kind, o_pct, o_cnt, o_pres;
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
+  DevBuf q_rlo, q_rhi, q_out, q_slot, q_key, q_key2, q_pos, q_pos2, q_head, q_incl, q_point, q_ptts, q_ptgrp;
+  DevBuf q_vlen, q_voff, q_vpos, q_tix;   // windowed accumulation: the spans' positions in output-group order, their entries
+  DevBuf q_caltab, q_spcal;         // calendar downsampling: boundary runs per span anchor
+  DevBuf q_gsp, q_spq, q_spts;      // greedy walk over spans out of time order (k_hist_walk)
+  DevBuf acc, pres, pkind, flag, ptout, err, pct;
+  DevBuf o_ts, o_grp, o_kind, o_pct, o_cnt, o_pres;
+  DevBuf tmp;                    // the scans' and sorts' temporary storage
+  // what hist_release hands back: policy, not ownership (deleting the store frees every buffer)
   void release() {
-    for (Buf* b : {&val, &voff, &codec, &status, &hkey, &hcount, &hidx, &dlo, &dup, &lkey, &lidx, &lkey2, &lidx2, &pos_cell, &pos_ts, &pos_kind,
+    for (DevBuf* b : {&val, &voff, &codec, &status, &hkey, &hcount, &hidx, &dlo, &dup, &lkey, &lidx, &lkey2, &lidx2, &pos_cell, &pos_ts, &pos_kind,
                    &row_pos, &col_lid, &lay_col, &lay_off, &lay_di, &q_rlo, &q_rhi, &q_out, &q_slot, &q_key, &q_key2, &q_pos, &q_pos2, &q_head, &q_incl,
                    &q_point, &q_ptts, &q_ptgrp, &q_vlen, &q_voff, &q_vpos, &q_tix, &q_caltab, &q_spcal, &q_gsp, &q_spq, &q_spts, &acc, &pres, &pkind, &flag, &ptout, &err, &pct, &o_ts, &o_grp,
                    &o_kind, &o_pct, &o_cnt, &o_pres})
       b->release();
-    if (tmp) (void)hipFree(tmp);
-    tmp = nullptr;
-    tmp_bytes = 0;
+    tmp.release();
   }
 };
 
@@ -269,15 +248,14 @@ extern "C" int tsdbhip_load_histograms(tsdbhip_ctx* c, const tsdbhip_hist_batch*
   }
   // bucket layouts: runs of columns with the same key bytes share one row of dictionary indices
   {
-    Buf head, excl;
-    struct Rel { Buf* a; Buf* b; ~Rel() { a->release(); b->release(); } } rel{&head, &excl};
+    DevBuf head, excl;
     HOK(head.ensure(NC * 4 + 4));
     HOK(excl.ensure(NC * 8 + 16));
     HOK(S->col_lid.ensure(NC * 4 + 4));
     HOK(S->lay_col.ensure(NC * 4 + 4));
     HOK(hist_layout_index(NC, S->voff.as<uint64_t>(), S->val.as<uint8_t>(), S->status.as<uint8_t>(), head.as<uint32_t>(),
-                          excl.as<int64_t>(), S->col_lid.as<int32_t>(), S->lay_col.as<int32_t>(), &S->n_layouts, &S->tmp,
-                          &S->tmp_bytes, st));
+                          excl.as<int64_t>(), S->col_lid.as<int32_t>(), S->lay_col.as<int32_t>(), &S->n_layouts, &S->tmp.p,
+                          &S->tmp.n, st));
     const int64_t NL = S->n_layouts;
     std::vector<int32_t> lcol(std::max<int64_t>(1, NL)), loff(std::max<int64_t>(1, NL) + 1, 0);
     if (NL) HOK(hipMemcpyAsync(lcol.data(), S->lay_col.p, NL * 4, hipMemcpyDeviceToHost, st));
@@ -612,7 +590,7 @@ int hist_run(tsdbhip_ctx* c, const tsdbhip_query* q, int64_t start, int64_t end,
     if (NP)
       HOK(hist_sparse(p, NP, S->q_key2.as<uint64_t>(), S->q_pos.as<uint32_t>(), S->q_pos2.as<uint32_t>(),
                       S->q_head.as<uint32_t>(), S->q_incl.as<int64_t>(), S->q_ptts.as<int64_t>(), S->q_ptgrp.as<int32_t>(),
-                      &n_points, &S->tmp, &S->tmp_bytes, st));
+                      &n_points, &S->tmp.p, &S->tmp.n, st));
     p.pt_ts = S->q_ptts.as<int64_t>();
     p.pt_group = S->q_ptgrp.as<int32_t>();
   } else {
@@ -643,7 +621,7 @@ int hist_run(tsdbhip_ctx* c, const tsdbhip_query* q, int64_t start, int64_t end,
     HOK(S->q_vpos.ensure(NP * 4 + 4));
     int64_t nvp = 0;
     HOK(hist_vpos(S->q_rlo.as<int64_t>(), S->q_rhi.as<int64_t>(), S->row_pos.as<int64_t>(), nsp, S->q_vlen.as<uint32_t>(),
-                  S->q_voff.as<int64_t>(), S->q_vpos.as<int32_t>(), &nvp, &S->tmp, &S->tmp_bytes, st));
+                  S->q_voff.as<int64_t>(), S->q_vpos.as<int32_t>(), &nvp, &S->tmp.p, &S->tmp.n, st));
     HOK(S->q_tix.ensure(nvp * 24 + 24));
     HOK(hist_accum_window(p, S->q_vpos.as<int32_t>(), nvp, S->lkey2.as<uint64_t>(), S->lidx2.as<int32_t>(), S->lslots,
                           S->q_tix.p, st));
@@ -653,7 +631,7 @@ int hist_run(tsdbhip_ctx* c, const tsdbhip_query* q, int64_t start, int64_t end,
   HOK(S->flag.ensure(n_points * 4 + 4));
   HOK(S->ptout.ensure(n_points * 8 + 16));
   HOK(hist_flags(p, S->flag.as<uint32_t>(), st));
-  HOK(hist_scan(S->flag.as<uint32_t>(), S->ptout.as<int64_t>(), n_points, &S->tmp, &S->tmp_bytes, st));
+  HOK(hist_scan(S->flag.as<uint32_t>(), S->ptout.as<int64_t>(), n_points, &S->tmp.p, &S->tmp.n, st));
   int64_t n_out = 0;
   HOK(hipMemcpyAsync(&n_out, S->ptout.as<int64_t>() + n_points, 8, hipMemcpyDeviceToHost, st));
   HOK(hipMemcpyAsync(err, S->err.p, 8, hipMemcpyDeviceToHost, st));

@@ -36,7 +36,7 @@ EXPORTS = [
     "tsdbhip_md_shard_mode", "tsdbhip_md_info", "tsdbhip_host_alloc", "tsdbhip_host_free", "tsdbhip_md_stats",
     "tsdbhip_device_count", "tsdbhip_set_option", "tsdbhip_get_option", "tsdbhip_preagg_run", "tsdbhip_preagg_download",
     "tsdbhip_regroup", "tsdbhip_append", "tsdbhip_debug_regular", "tsdbhip_trim", "tsdbhip_debug_layout",
-    "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct",
+    "tsdbhip_debug_loaded", "tsdbhip_upsert", "tsdbhip_debug_rollup", "tsdbhip_debug_pct", "tsdbhip_debug_buffers",
     "tsdbhip_remove", "tsdbhip_last", "tsdbhip_put",
     "tsdbhip_tags_load", "tsdbhip_tags_loaded", "tsdbhip_regroup_tags", "tsdbhip_tags_keys",
 ]
@@ -171,6 +171,7 @@ def lib():
         L.tsdbhip_debug_sel_window.argtypes = [vp, C.c_void_p, C.c_void_p]
         L.tsdbhip_debug_rollup.argtypes = [vp, C.c_void_p]
         L.tsdbhip_debug_pct.argtypes = [vp, C.c_void_p]
+        L.tsdbhip_debug_buffers.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_uint64)] * 2
         L.tsdbhip_shard_bounds.argtypes = [C.POINTER(abi.Batch), C.c_int, C.c_int, C.c_void_p]
         L.tsdbhip_load_shard.argtypes = [vp, C.POINTER(abi.Batch), C.c_int, C.c_int64, C.c_int64]
         L.tsdbhip_synth_shard.argtypes = [vp, C.POINTER(abi.SynthSpec), C.c_int64, C.c_int64]
@@ -211,6 +212,14 @@ def get_option(name: str) -> int:
     v = C.c_int64()
     _check(lib().tsdbhip_get_option(name.encode(), C.byref(v)))
     return v.value
+
+
+def debug_buffers() -> abi.BufferCounts:
+    """tsdbhip_debug_buffers: live device buffers and their bytes, live page-locked buffers and
+    theirs, over every context of the process (tests: a closed engine leaves none behind)."""
+    dn, db, hn, hb = C.c_int64(), C.c_uint64(), C.c_int64(), C.c_uint64()
+    _check(lib().tsdbhip_debug_buffers(C.byref(dn), C.byref(db), C.byref(hn), C.byref(hb)))
+    return abi.BufferCounts(dn.value, db.value, hn.value, hb.value)
 
 
 def reset_options() -> None:
